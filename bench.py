@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BLS-verify witness instances/sec (full pairing circuit) on MI355X.
 
-One "step" = one pass of the hot path (every witness of the circuit of /root/reference/src/constraints.rs:335-366, for
+One "step" = one pass of the hot path (every witness of the circuit of the reference's src/constraints.rs:335-366, for
 each instance) over one batch of 1 024 synthetic (pk, msg, sig) instances (BASELINE.json configs[1]). Inputs are resident
 in HBM before the timed region; every step writes a complete [1024][n_witness] witness tensor (34 MB per instance).
 
@@ -30,13 +30,8 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The library needs no runtime environment. This harness sets ONE variable for its own process, before HIP is initialised: the runtime backs the
-# streams of each priority level with GPU_MAX_HW_QUEUES (default 4) hardware queues, and streams that share a queue serialise. One rank has the
-# null stream + up to three group buffers' main streams at normal priority; the all-gather legs add a communication stream and the process
-# group's own RCCL stream: with four queues two of them share one, and a marker behind a waiting command starts the next launch group ~70 ms
-# late (profiles/r04_consumer_timeline.txt). Eight queues per level remove the aliasing; measured neutral to +1 % at N = 1
-# (profiles/r04_consumer_probe.txt, block 3). A value the caller has set is kept.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The library needs no runtime environment, and this harness sets none: it runs with the runtime's own number of hardware queues per
+# priority level (a shared GPU caps it; more queues per process measured neutral to +1 % at N = 1, profiles/r04_consumer_probe.txt, block 3).
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured float4 copy)
 # algorithmic field work per instance, from the oracle's op counter on the reference gadget case
@@ -48,6 +43,8 @@ FPMUL_PER_INV = 570
 # 636 of the 940 cofactor-chain inversions are shared with a neighbour (Montgomery's trick: +9 products each, -1 inversion)
 FPMUL_PER_INV_EXECUTED = 27
 TRAFFIC_FILES = ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json")
+DUMP_SAMPLE = 1 << 19  # witness elements in --dump-outputs' sample: 48 MiB of float64, the files stay under 64 MB
+DUMP_SEED = 0x5EED
 
 
 def parse_args():
@@ -77,6 +74,9 @@ def parse_args():
                     "the compact wire form of configs[1], each with its own roofline and CPU baseline (0 = skip)")
     ap.add_argument("--allgather-form", choices=("compact", "full"), default="compact",
                     help="what travels in the all-gather leg: the compact wire form, expanded by every receiver, or the full witness tensors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all): results, "
+                         "the digest of every instance's witness vector, and a fixed seeded sample of witness elements")
     return ap.parse_args()
 
 
@@ -97,6 +97,39 @@ def spawn_ranks(args):
     else:
         sys.stderr.write(p.stdout)
     sys.exit(p.returncode if p.returncode or lines else 1)
+
+
+def u64_to_f64(a):
+    """u64 words -> float64 pairs (low 32 bits, high 32 bits): exact, every u32 is a float64 integer."""
+    import numpy as np
+
+    a = np.ascontiguousarray(a).view(np.uint64)
+    return np.stack([a & 0xFFFFFFFF, a >> 32], axis=-1).astype(np.float64).reshape(a.shape[:-1] + (2 * a.shape[-1],))
+
+
+def dump_outputs(pkg, out_dir, witness, result, rank=0, world=1):
+    """What one engine step hands its caller, as float64 .npy files under out_dir (rank r > 0 of a multi-GPU run adds _rank<r>):
+      result          [n]           the verdict of every instance (0 / 1)
+      witness_digest  [n, 4]        blsw_witness_digest of every instance's whole witness vector (two u64 as four u32)
+      witness_sample  [S, 12]       S witness elements (instance, index) drawn with a fixed seed from the whole tensor, as 12 u32 limbs each
+    The sample is shared out over the ranks, so that the files of a multi-GPU run also stay under 64 MB in all."""
+    import numpy as np
+    import torch
+
+    n, n_witness = witness.shape[0], witness.shape[1]
+    rng = np.random.default_rng(DUMP_SEED)
+    s = max(1, DUMP_SAMPLE // max(1, world))
+    inst = rng.integers(0, n, size=s, dtype=np.int64)
+    idx = rng.integers(0, n_witness, size=s, dtype=np.int64)
+    sample = witness[torch.from_numpy(inst).to(witness.device), torch.from_numpy(idx).to(witness.device)]  # [s, 6] int64
+    arrays = {"result": result[:n].cpu().numpy().astype(np.float64),
+              "witness_digest": u64_to_f64(pkg.witness_digest(witness).cpu().numpy()),
+              "witness_sample": u64_to_f64(sample.cpu().numpy())}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def balanced_coalesce(steps, max_group):
@@ -579,6 +612,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if eng.materialised() != args.warmup + args.steps:
+        raise SystemExit("bench.py: the engine materialised %d steps, %d were submitted" % (eng.materialised(), args.warmup + args.steps))
+    dumped = None
+    if args.dump_outputs:  # the ring slot of the last timed step, before anything below reuses the ring
+        last = (args.warmup + args.steps - 1) % n_out
+        dumped = dump_outputs(pkg, args.dump_outputs, outs[last], results[last], rank=rank, world=world)
 
     # live measurement of the dominant-by-bytes kernel (k_sha_expand): HIP events recorded around it on the stream it
     # ran on, for every launch of the timed region (at most 1024)
@@ -732,6 +771,8 @@ def main():
         tot = whole_step["write_bytes"] + whole_step["fetch_bytes"]
         out["roofline_hbm_total"] = {"bound": "hbm", "traffic_per_step": tot, "achieved": tot / (dt / args.steps) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                      "frac": tot / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS, "source": "profiles/%s whole_step (rocprofv3 --pmc passes)" % whole_step_file}
+    if dumped:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1, "arrays": dumped}
     out["witness_ok"] = witness_ok  # digests of the ring tensors after the timed region == a direct-mode engine's on the same batch
     if consumer:
         out["value_consumer_mode"] = consumer.get("value")

@@ -55,3 +55,45 @@ def test_group_balancing_and_cpu_share(bench):
     assert bench.balanced_coalesce(20, 16) == 10 and bench.balanced_coalesce(1024, 16) == 16 and bench.balanced_coalesce(5, 16) == 5
     assert bench.balanced_coalesce(33, 16) == 11
     assert 1 <= bench.host_cores() <= (os.cpu_count() or 1)
+
+
+def test_dump_outputs_files_exact_and_seeded(bench, tmp_path, monkeypatch):
+    """--dump-outputs host logic on a small CPU tensor: float64 files under 64 MB, u64 words split exactly into u32 halves, the witness sample
+    drawn from the whole tensor with a fixed seed (the same files twice), ranks of a multi-GPU run sharing the budget."""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", str(tmp_path)])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.dump_outputs == str(tmp_path)
+    words = np.array([0, 1, 2**32 - 1, 2**32, 2**63 + 5, 2**64 - 1], dtype=np.uint64)
+    halves = bench.u64_to_f64(words.reshape(1, 6))
+    assert halves.dtype == np.float64 and halves.shape == (1, 12)
+    assert [int(halves[0, 2 * i]) + (int(halves[0, 2 * i + 1]) << 32) for i in range(6)] == [int(x) for x in words]
+
+    class Pkg:
+        @staticmethod
+        def witness_digest(w):
+            return w.sum(dim=1)[:, :2]
+
+    n, nw = 5, 37
+    rng = np.random.default_rng(1)
+    w = torch.from_numpy(rng.integers(-2**63, 2**63 - 1, size=(n, nw, 6), dtype=np.int64))
+    res = torch.tensor([1, 0, 1, 1, 0], dtype=torch.int32)
+    shapes = bench.dump_outputs(Pkg, str(tmp_path / "a"), w, res)
+    bench.dump_outputs(Pkg, str(tmp_path / "b"), w, res)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["result.npy", "witness_digest.npy", "witness_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10**6
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "result.npy").tolist() == [1, 0, 1, 1, 0]
+    sample = np.load(tmp_path / "a" / "witness_sample.npy")
+    assert shapes["witness_sample"] == list(sample.shape) and sample.shape[1] == 12
+    limbs = (sample[:, 0::2].astype(np.uint64) | (sample[:, 1::2].astype(np.uint64) << np.uint64(32)))
+    elems = {tuple(r) for r in w.numpy().view(np.uint64).reshape(-1, 6).tolist()}
+    assert all(tuple(r) in elems for r in limbs.tolist())
+    assert len({tuple(r) for r in limbs.tolist()}) == n * nw  # the sample reaches every element of a small tensor
+    bench.dump_outputs(Pkg, str(tmp_path / "c"), w, res, rank=1, world=2)
+    assert np.load(tmp_path / "c" / "witness_sample_rank1.npy").shape[0] == sample.shape[0] // 2

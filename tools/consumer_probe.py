@@ -8,8 +8,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# as bench.py: more hardware queues per priority level than the runtime's default of 4, so that the engine's streams and the consumer's do not share one
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 
 def main():
