@@ -66,7 +66,6 @@ inline int stream_device(hipStream_t st) {
 // consumer has released its output's previous user, so the 34 MB vectors exist only between expansion and consumption and
 // the output ring can be smaller than a group. A step can also leave in compact form (its slices of the staging, copied).
 #define BLSW_MAX_BUFFERS 32
-#define BLSW_MILLER_CHUNK_DEFAULT 12   // pairs per lane of the pair-parallel Miller product (blsw_verify_multi_batch)
 #define BLSW_MILLER_PAR_MIN_PAIRS 8  // below: the serial six-lane team kernel
 // clear_cofactor2 on three lanes per pair halves the chain's latency and costs 38 % more products in it: it pays while the launch is
 // latency-bound (an 8 192-instance shard in groups of 4: +16 %; one 128-pair instance: 88 -> 60 ms) and costs 1-4 % once the group's
@@ -98,6 +97,14 @@ struct Job {  // materialisation of one step: bit expansion + field placement in
     int buf;
     uint32_t s;
 };
+// BLSW_TRACE_GROUP=1 (diagnostic; not an option of the ABI): timing events after the stages of the K == 1 main stream of every launch group, printed to
+// stderr when the engine is destroyed — what a kernel trace shows, without a profiler attached
+struct GroupTrace {
+    static constexpr int kMarks = 6;
+    hipEvent_t ev[kMarks];
+    uint64_t lanes;
+    bool lat;
+};
 struct blsw_engine {
     uint64_t n = 0;
     uint32_t msg_len = 0, max_steps = 0;
@@ -125,6 +132,7 @@ struct blsw_engine {
     bool staged = false;  // false: direct mode (max_steps == 1, no staging; witnesses written in place by the chains)
     bool chains_inlined = false;  // which compilation of the chain kernels (options.chain_variant; kcommon.hpp: BLSW_K)
     uint32_t cofactor_mode = 0;  // clear_cofactor2 with its three chunks on three lanes: 0 by group size, 1 never, 2 always (options.cofactor_mode)
+    std::vector<GroupTrace> trace;  // BLSW_TRACE_GROUP
 };
 
 static void engine_free(blsw_engine* e) {
@@ -205,6 +213,10 @@ static void launch_canonical(blsw_engine* e, hipStream_t st, uint64_t* out, uint
     const uint32_t K = e->L.n_pairs, rows = e->L.n_witness - K * e->L.sha_bits;
     hipLaunchKernelGGL(k_canonical_rows, dim3((rows + 255) / 256, (unsigned)e->n), dim3(256), 0, st, out, out_stride, e->L.off_expand, e->L.sha_bits, rows, K, e->L.stride_hash);
 }
+// bit expansion in the engine's variant (options.expand_variant / expand_store / place_lds)
+static void engine_expand(const blsw_engine* e, hipStream_t st, const ExpandArgs& xa, unsigned n_y) {
+    launch_expand(e->opt.expand_variant, e->opt.expand_store, e->opt.place_lds, st, xa, n_y);
+}
 
 static int consumed_slot(blsw_engine* e, const void* ptr) {
     for (int c = 0; c < BLSW_MAX_CONSUMED; c++)
@@ -262,9 +274,7 @@ static void materialise(blsw_engine* e, int k, uint32_t s) {
         // Consumer mode only: a free-running engine has all of the group's expansions to write, and holding them back is HBM time lost (configs[3],
         // 12 steps: 950 instead of 1 050 instances/s).
         if (b.lat_group && e->opt.consumer_mode) hipStreamWaitEvent(e->expand, b.ev_cof[2 * BLSW_COFV_NSEG + 3], 0);
-        const uint32_t variant = e->opt.expand_variant;
-        const unsigned lds = e->opt.place_lds;
-        launch_expand(variant, e->opt.expand_store, lds, e->expand, xa, (unsigned)(e->n * K));
+        engine_expand(e, e->expand, xa, (unsigned)(e->n * K));
         if (timed) {
             hipEventRecord(e->ev_exp[2 * e->n_timed + 1], e->expand);
             e->n_timed++;
@@ -323,15 +333,6 @@ static int pump(blsw_engine* e) {
     return hip_ok(hipGetLastError(), "materialise");
 }
 
-// BLSW_TRACE_GROUP=1 (diagnostic; not an option of the ABI): timing events after the stages of the K == 1 main stream of every launch group, printed to
-// stderr when the engine is destroyed — what a kernel trace shows, without a profiler attached
-struct GroupTrace {
-    static constexpr int kMarks = 6;
-    hipEvent_t ev[kMarks];
-    uint64_t lanes;
-    bool lat;
-};
-static std::vector<GroupTrace> g_group_trace;
 static bool group_trace_on() {
     static const bool on = getenv("BLSW_TRACE_GROUP") != nullptr;
     return on;
@@ -341,9 +342,9 @@ static void group_trace_mark(GroupTrace* t, int i, hipStream_t st) {
     hipEventCreate(&t->ev[i]);
     hipEventRecord(t->ev[i], st);
 }
-static void group_trace_dump() {
+static void group_trace_dump(blsw_engine* e) {
     static const char* names[GroupTrace::kMarks - 1] = {"sha_values+map", "cofactor", "prepare(H)", "wait aux", "pairing"};
-    for (const GroupTrace& t : g_group_trace) {
+    for (const GroupTrace& t : e->trace) {
         hipEventSynchronize(t.ev[GroupTrace::kMarks - 1]);
         fprintf(stderr, "[blsw group] %llu lanes%s:", (unsigned long long)t.lanes, t.lat ? " (latency kernels)" : "");
         float total = 0;
@@ -356,7 +357,24 @@ static void group_trace_dump() {
         fprintf(stderr, " | total %.2f ms\n", total);
         for (hipEvent_t ev : t.ev) hipEventDestroy(ev);
     }
-    g_group_trace.clear();
+    e->trace.clear();
+}
+
+// the N = steps * n * K lanes of `steps` batches of n instances of K pairs over workspace `ws`; as a direct call runs them: the layout is also the
+// staging layout, no raised priority, instance variables as Montgomery limbs
+static Group make_group(uint64_t steps, uint64_t n, uint32_t K, uint32_t msg_len, const StepDesc* desc, const blsw_layout_t& L, const Workspace& ws) {
+    Group g;
+    g.N = steps * n * K;
+    g.n = (uint32_t)n;
+    g.K = K;
+    g.msg_len = msg_len;
+    g.desc = desc;
+    g.L = L;
+    g.LS = L;
+    g.ws = ws;
+    g.chain_prio = 0;
+    g.canonical = 0;
+    return g;
 }
 
 static int launch_group(blsw_engine* e) {
@@ -364,17 +382,15 @@ static int launch_group(blsw_engine* e) {
     const uint32_t steps = e->pending;
     if (steps == 0) return BLSW_OK;
     const uint32_t K = e->L.n_pairs;  // (pk, msg) pairs per instance: 1 except for the N+1-pair product
-    Group g;  // per-pair view: one lane per (instance, pair)
-    g.N = (uint64_t)steps * e->n * K;
-    g.n = (uint32_t)e->n;
-    g.K = K;
-    g.msg_len = e->msg_len;
-    g.desc = b.d_desc;
-    g.L = e->L;
+    // per-pair view: one lane per (instance, pair)
+    Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->L, e->staged, e->modes, (uint64_t)steps * e->n));
     g.LS = e->LS;
-    g.ws = carve(b.base, g.N, e->L, e->staged, e->modes, (uint64_t)steps * e->n);
     g.chain_prio = e->opt.prio_mode == 0;
     g.canonical = (int)e->opt.output_form;
+    // per-signature view (the same group for K == 1): the signature's chains and the Miller product on steps * n lanes
+    Group gs = g;
+    gs.N = (uint64_t)steps * e->n;
+    gs.K = 1;
     const unsigned g1 = (unsigned)((g.N + 63) / 64);
     const unsigned gt = (unsigned)((g.N + BLSW_TEAMS_PER_WAVE - 1) / BLSW_TEAMS_PER_WAVE);
     // Which kernels. A SMALL group (at most BLSW_LATENCY_MAX_LANES lanes) that finds the engine's chains idle starts a pipeline: nothing of this engine
@@ -398,14 +414,7 @@ static int launch_group(blsw_engine* e) {
     // ... and the pipelines of its chunks run beside the doubling chain on the buffer's main stream (the segments' points) and the engine's sha and
     // place streams (the addition chains): streams with nothing to do while a cold group's chains run (its SHA bits are enqueued before; placement
     // starts after the chains)
-    CofactorSide cof_side;
-    cof_side.side = b.st[1];
-    cof_side.pts = b.st[0];
-    cof_side.acc[0] = e->place;
-    cof_side.acc[1] = e->sha;
-    for (int i = 0; i < BLSW_COFV_NSEG; i++) cof_side.ev_seg[i] = b.ev_cof[i], cof_side.ev_pts[i] = b.ev_cof[BLSW_COFV_NSEG + i];
-    for (int i = 0; i < 3; i++) cof_side.ev_acc[i] = b.ev_cof[2 * BLSW_COFV_NSEG + i];
-    cof_side.ev_join = b.ev_cof[2 * BLSW_COFV_NSEG + 3];
+    const CofactorSide cof_side = cofactor_side(b.st[1], b.st[0], e->place, e->sha, b.ev_cof);
     const bool cof_deferred = lat.vf && g.ws.cofv != nullptr;
     // the waves of a latency group's critical path (hash-to-G2, prepare(H), pairing) raise their priority: the streams beside them — the first
     // expansions, the next group's chains, this group's aux chains — have slack, they have none
@@ -417,7 +426,6 @@ static int launch_group(blsw_engine* e) {
     // buffer's own main stream carries the points of the cofactor segments instead.
     const bool lat_any = lat.quad || lat.vf;
     hipStream_t st = lat_any ? e->lat : b.st[0];
-    GroupTrace* trace = nullptr;
     // inputs of every step are ready once its submitting stream reached the point of the submit
     for (uint32_t s = 0; s < steps; s++) hipStreamWaitEvent(st, b.ev_in[s], 0);
     bool any_out = false;
@@ -433,83 +441,47 @@ static int launch_group(blsw_engine* e) {
     hipStreamWaitEvent(e->sha, b.ev_start, 0);
     if (any_out) hipLaunchKernelGGL(ck.sha, dim3(g1), dim3(64), 0, e->sha, g, 1, 0);
     hipEventRecord(b.ev_sha, e->sha);
-    if (K > 1) {  // N+1-pair product: per-pair chains on N = steps * n * K lanes, per-signature chains and the Miller product on steps * n
-        Group gs = g;
-        gs.N = (uint64_t)steps * e->n;
-        gs.K = 1;
-        hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, gm);
-        launch_map(ck, lat, gm, st);
-        launch_cofactor(ck, lat, chunked, gm, st, &cof_side);
-        launch_prepare(ck, lat, gm, 0, st);
-        // aux: what the Miller product waits for (prepare(sig), the keys' prepare_g1) first, then the signature's allocation chain, which only the
-        // end of the group waits for (ev_side)
-        launch_prepare(ck, lat, gs, 1, b.st[1]);
-        hipLaunchKernelGGL(ck.g1, dim3(g1), dim3(64), 0, b.st[1], g);
-        hipEventRecord(b.ev_aux, b.st[1]);
-        launch_g2_alloc(ck, lat, gs, b.st[1]);
-        hipStreamWaitEvent(st, b.ev_aux, 0);
-        if (cof_deferred) launch_cofactor_witness(lat, g, cof_side);
-        if (K < BLSW_MILLER_PAR_MIN_PAIRS) {
-            hipLaunchKernelGGL(k_pairing_team_multi, dim3((unsigned)((gs.N + BLSW_TEAMS_PER_WAVE - 1) / BLSW_TEAMS_PER_WAVE)), dim3(64), 0, st, gs, K, g.N);
-        } else {
-            MillerParArgs ma;
-            ma.K = K;
-            ma.B = BLSW_MILLER_CHUNK_DEFAULT;
-            ma.C = (K + ma.B - 1) / ma.B;
-            ma.n_h = g.N;
-            ma.spine_lane = 0;
-            char* p = reinterpret_cast<char*>(b.base) + align_up(g.ws.total_bytes, 256);
-            auto take = [&](uint64_t items) {
-                Fp* r = reinterpret_cast<Fp*>(p);
-                p += align_up(items * 12 * sizeof(Fp), 256);
-                return r;
-            };
-            ma.cprod = take(gs.N * 68 * ma.C);
-            ma.q = take(gs.N * 68 * ma.C);
-            ma.t = take(gs.N * 68);
-            ma.f1 = take(gs.N * 68);
-            ma.ffinal = take(gs.N);
-            launch_miller_par(gs, ma, st, nullptr, nullptr, nullptr);  // one stream: other groups run beside this one
-        }
-    } else {
-        // main, first part: the hash-to-G2 critical path
-        if (group_trace_on()) {
-            g_group_trace.push_back(GroupTrace{{}, g.N, lat.quad || lat.vf});
-            trace = &g_group_trace.back();
-        }
-        group_trace_mark(trace, 0, st);
-        hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, gm);
-        launch_map(ck, lat, gm, st);
-        group_trace_mark(trace, 1, st);
-        launch_cofactor(ck, lat, chunked, gm, st, &cof_side);
-        group_trace_mark(trace, 2, st);
-        launch_prepare(ck, lat, gm, 0, st);
-        group_trace_mark(trace, 3, st);
-        // aux: prepare_g2(sig) and the key's allocation + prepare_g1 — what the pairing waits for (ev_aux) — then the signature's allocation chain, which
-        // only the end of the group waits for (ev_side): the longest aux kernel no longer delays the pairing of a latency-bound group
-        hipStream_t sb = b.st[1];
-        launch_prepare(ck, lat, g, 1, sb);
-        if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
-            hipLaunchKernelGGL(ck.agg_keys, dim3((unsigned)((g.N * e->L.n_keys + 63) / 64)), dim3(64), 0, sb, g, g.ws.keyproj);
-            hipLaunchKernelGGL(ck.agg_sum, dim3(g1), dim3(64), 0, sb, g, (const Fp*)g.ws.keyproj);
-        } else  // params_mode: lanes [N, 2 N) allocate and prepare the generator (k_g1)
-            hipLaunchKernelGGL(ck.g1, dim3(e->L.params_mode ? (unsigned)((2 * g.N + 63) / 64) : g1), dim3(64), 0, sb, g);
-        hipEventRecord(b.ev_aux, sb);
-        if (e->L.sig_mode) {
-            // SignatureVar::new_variable(Input): no allocation chain (prepare(sig) wrote the instance variables)
-        } else if (e->modes.g2_team)
-            hipLaunchKernelGGL(k_g2_alloc_team, dim3(gt), dim3(64), 0, b.st[1], g);
-        else
-            launch_g2_alloc(ck, lat, g, b.st[1]);
+    GroupTrace* trace = nullptr;
+    if (K == 1 && group_trace_on()) {
+        e->trace.push_back(GroupTrace{{}, g.N, lat_any});
+        trace = &e->trace.back();
     }
-    if (K == 1) {
-        if (cof_deferred) launch_cofactor_witness(lat, g, cof_side);
-        // main, second part: the pairing
-        hipStreamWaitEvent(st, b.ev_aux, 0);
-        group_trace_mark(trace, 4, st);
+    // main, first part: the hash-to-G2 critical path (per pair)
+    group_trace_mark(trace, 0, st);
+    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, gm);
+    launch_map(ck, lat, gm, st);
+    group_trace_mark(trace, 1, st);
+    launch_cofactor(ck, lat, chunked, gm, st, &cof_side);
+    group_trace_mark(trace, 2, st);
+    launch_prepare(ck, lat, gm, 0, st);
+    group_trace_mark(trace, 3, st);
+    // aux: prepare_g2(sig) and the keys' allocation + prepare_g1 — what the pairing waits for (ev_aux) — then the signature's allocation chain, which
+    // only the end of the group waits for (ev_side): the longest aux kernel no longer delays the pairing of a latency-bound group
+    hipStream_t sb = b.st[1];
+    launch_prepare(ck, lat, gs, 1, sb);
+    if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
+        hipLaunchKernelGGL(ck.agg_keys, dim3((unsigned)((g.N * e->L.n_keys + 63) / 64)), dim3(64), 0, sb, g, g.ws.keyproj);
+        hipLaunchKernelGGL(ck.agg_sum, dim3(g1), dim3(64), 0, sb, g, (const Fp*)g.ws.keyproj);
+    } else  // one lane per key (per pair); params_mode: lanes [N, 2 N) allocate and prepare the generator (k_g1)
+        hipLaunchKernelGGL(ck.g1, dim3(e->L.params_mode ? (unsigned)((2 * g.N + 63) / 64) : g1), dim3(64), 0, sb, g);
+    hipEventRecord(b.ev_aux, sb);
+    if (e->L.sig_mode) {
+        // SignatureVar::new_variable(Input): no allocation chain (prepare(sig) wrote the instance variables)
+    } else if (e->modes.g2_team)
+        hipLaunchKernelGGL(k_g2_alloc_team, dim3(gt), dim3(64), 0, sb, g);
+    else
+        launch_g2_alloc(ck, lat, gs, sb);
+    if (cof_deferred) launch_cofactor_witness(lat, g, cof_side);
+    // main, second part: the pairing
+    hipStreamWaitEvent(st, b.ev_aux, 0);
+    group_trace_mark(trace, 4, st);
+    if (K == 1)
         launch_pairing(gm, e->modes, st);
-        group_trace_mark(trace, 5, st);
-    }
+    else if (K < BLSW_MILLER_PAR_MIN_PAIRS)  // N+1-pair product: the Miller product per signature over its K pairs
+        hipLaunchKernelGGL(k_pairing_team_multi, dim3((unsigned)((gs.N + BLSW_TEAMS_PER_WAVE - 1) / BLSW_TEAMS_PER_WAVE)), dim3(64), 0, st, gs, K, g.N);
+    else  // one stream: other groups run beside this one
+        launch_miller_par(gs, carve_miller_par(reinterpret_cast<char*>(b.base) + align_up(g.ws.total_bytes, 256), gs.N, K), st, nullptr, nullptr, nullptr);
+    group_trace_mark(trace, 5, st);
     // the group's chains are done when the aux stream's tail (G2 allocation, deferred witness phases of the cofactor chain) is
     hipEventRecord(b.ev_side, b.st[1]);
     hipStreamWaitEvent(st, b.ev_side, 0);
@@ -520,7 +492,7 @@ static int launch_group(blsw_engine* e) {
     b.jobs_left = steps;
     for (uint32_t s = 0; s < steps; s++) e->jobs.push_back({e->cur, s});
     b.used = true;
-    b.lat_group = lat.quad || lat.vf;
+    b.lat_group = lat_any;
     b.first_seq = e->launched;
     b.steps = steps;
     e->launched += steps;
@@ -531,45 +503,64 @@ static int launch_group(blsw_engine* e) {
     return pump(e);
 }
 
-// Side streams of a DIRECT call's values-first cofactor chain (kcommon.hpp: CofactorSide), created once per host thread and device and kept (an event
-// is re-recorded per call; a wait refers to the record that preceded it). Without them the segments' phases run one after the other on the caller's stream.
-struct DirectLanes {
-    int device = -1;
-    hipStream_t st[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev[BLSW_COFV_EVENTS + 1] = {};
-    bool ok = false;
+// Side streams of the direct calls, created once per host thread and device and kept (an event is re-recorded per call; a wait refers to the record
+// that preceded it). nullptr if they could not be created: the caller's stream then carries everything.
+struct SideLanes {
+    hipStream_t aux[3];                      // blsw_verify_multi_batch: the signature's chains, the keys' allocation, the SHA bits and their expansion
+    hipStream_t cof[4];                      // a values-first cofactor chain's side, pts, acc[0], acc[1] (kcommon.hpp: CofactorSide)
+    hipEvent_t ev_fork, ev_join[3];          // the fork from the caller's stream to aux, the joins of aux
+    hipEvent_t ev_cof[BLSW_COFV_EVENTS + 1];  // CofactorSide's events, and the join of its side stream
+    bool made, ok;
 };
-static DirectLanes* direct_lanes(int dev) {
-    static thread_local std::map<int, DirectLanes> lanes;
-    DirectLanes& d = lanes[dev];
-    if (d.device != dev) {
-        d.device = dev;
-        d.ok = true;
-        for (hipStream_t& q : d.st) d.ok = d.ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
-        for (hipEvent_t& ev : d.ev) d.ok = d.ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+static SideLanes* side_lanes(int dev) {
+    static thread_local std::map<int, SideLanes> pool;
+    SideLanes& l = pool[dev];
+    if (!l.made) {
+        l.made = l.ok = true;
+        for (hipStream_t& q : l.aux) l.ok = l.ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
+        for (hipStream_t& q : l.cof) l.ok = l.ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
+        hipEvent_t* events[] = {&l.ev_fork, &l.ev_join[0], &l.ev_join[1], &l.ev_join[2]};
+        for (hipEvent_t* ev : events) l.ok = l.ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
+        for (hipEvent_t& ev : l.ev_cof) l.ok = l.ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
     }
-    return d.ok ? &d : nullptr;
+    return l.ok ? &l : nullptr;
 }
 // launch_cofactor of a direct call on `st`, with its pipelines on the thread's side streams; `st` has waited for all of it on return
 static void launch_cofactor_direct(const ChainKernels& ck, Latency lat, const Group& g, hipStream_t st, int dev) {
     const bool chunked = g.N <= BLSW_COFACTOR_CHUNKED_MAX_LANES;
-    DirectLanes* d = (lat.vf && g.ws.cofv) ? direct_lanes(dev) : nullptr;
+    SideLanes* d = (lat.vf && g.ws.cofv) ? side_lanes(dev) : nullptr;
     if (!d) {
         launch_cofactor(ck, lat, chunked, g, st);
         return;
     }
-    CofactorSide cs;
-    cs.side = d->st[0];
-    cs.pts = d->st[1];
-    cs.acc[0] = d->st[2];
-    cs.acc[1] = d->st[3];
-    for (int i = 0; i < BLSW_COFV_NSEG; i++) cs.ev_seg[i] = d->ev[i], cs.ev_pts[i] = d->ev[BLSW_COFV_NSEG + i];
-    for (int i = 0; i < 3; i++) cs.ev_acc[i] = d->ev[2 * BLSW_COFV_NSEG + i];
-    cs.ev_join = d->ev[2 * BLSW_COFV_NSEG + 3];
+    const CofactorSide cs = cofactor_side(d->cof[0], d->cof[1], d->cof[2], d->cof[3], d->ev_cof);
     launch_cofactor(ck, lat, chunked, g, st, &cs);
     launch_cofactor_witness(lat, g, cs);
-    hipEventRecord(d->ev[BLSW_COFV_EVENTS], cs.side);
-    hipStreamWaitEvent(st, d->ev[BLSW_COFV_EVENTS], 0);
+    hipEventRecord(d->ev_cof[BLSW_COFV_EVENTS], cs.side);
+    hipStreamWaitEvent(st, d->ev_cof[BLSW_COFV_EVENTS], 0);
+}
+
+// Every rule on an engine's arguments and options that does not need the device: blsw_engine_workspace_bytes_ex and blsw_engine_create_ex
+// refuse the same sets (BLSW_ERR_ARG)
+static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* o) {
+    // n is the y extent of the expansion / canonical-form launches (one row of workgroups per instance): at most 65535
+    if (!o || n == 0 || n > 65535 || max_steps == 0 || n_buffers == 0 || n_buffers > BLSW_MAX_BUFFERS || msg_len > 65535) return BLSW_ERR_ARG;
+    const bool staged = max_steps > 1 || n_buffers > 1;
+    // consumer mode is late materialisation out of the staging: a direct-mode engine (one step, one buffer) writes its witnesses in
+    // place while the chains run and could not honour a held output
+    if (o->consumer_mode > 1 || (o->consumer_mode == 1 && !staged)) return BLSW_ERR_ARG;
+    if (o->pairing_mode > 1 || o->g2_mode > 1 || (o->g2_mode == 1 && o->pairing_mode != 0) || o->expand_store > 3 || o->prio_mode > 2 || o->group_ramp > 1 ||
+        o->latency_mode > 4 || o->output_form > 1 || o->chain_variant > 2 || o->cofactor_mode > 2 || (o->expand_variant & 0xff) > 13 || (o->expand_variant >> 9) ||
+        o->n_keys > 65535 || (o->n_keys && o->g2_mode) || o->n_pairs > 4096)
+        return BLSW_ERR_ARG;
+    // N+1-pair product (options.n_pairs = K > 1): a staged engine with the default kernel modes; its expansion launch has one row of
+    // workgroups per (instance, pair)
+    if (o->n_pairs > 1 && (o->n_keys || o->pairing_mode || o->g2_mode || !staged || n * o->n_pairs > 65535)) return BLSW_ERR_ARG;
+    // ParametersVar allocated as witnesses: the single-key circuit with the six-lane pairing kernel (k_pairing_team_pv)
+    if (o->params_mode > 1 || (o->params_mode && (o->n_keys || o->n_pairs > 1 || o->pairing_mode))) return BLSW_ERR_ARG;
+    // PublicKeyVar / SignatureVar allocated as public inputs: the single-key circuit with Constant parameters and the one-lane G2 kernels
+    if (o->pk_mode > 1 || o->sig_mode > 1 || ((o->pk_mode || o->sig_mode) && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
+    return BLSW_OK;
 }
 
 extern "C" {
@@ -618,11 +609,8 @@ int blsw_engine_options_default(blsw_engine_options_t* o) {
 }
 
 int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options, uint64_t* bytes) {
-    if (!bytes || n == 0 || max_steps == 0 || n_buffers == 0 || n_buffers > BLSW_MAX_BUFFERS || msg_len > 65535 || !options || options->n_keys > 65535 ||
-        options->n_pairs > 4096 || (options->n_pairs > 1 && options->n_keys) || options->params_mode > 1 ||
-        (options->params_mode && (options->n_keys || options->n_pairs > 1 || options->pairing_mode)) || options->pk_mode > 1 || options->sig_mode > 1 ||
-        ((options->pk_mode || options->sig_mode) && (options->n_keys || options->n_pairs > 1 || options->params_mode || options->g2_mode)))
-        return BLSW_ERR_ARG;
+    if (!bytes) return BLSW_ERR_ARG;
+    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
     blsw_layout_t L;
     const uint32_t K = options->n_pairs > 1 ? options->n_pairs : 1;
     make_layout(msg_len, &L, options->n_keys, K, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1);
@@ -641,7 +629,7 @@ int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_st
             need = t > need ? t : need;
         }
     }
-    if (K > 1) need = align_up(need, 256) + miller_par_bytes(n * max_steps, K, BLSW_MILLER_CHUNK_DEFAULT);  // value stores of the pair-parallel Miller product
+    if (K > 1) need = align_up(need, 256) + miller_par_bytes(n * max_steps, K);  // value stores of the pair-parallel Miller product
     *bytes = (uint64_t)n_buffers * align_up(need, 4096);
     return BLSW_OK;
 }
@@ -653,26 +641,8 @@ int blsw_engine_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t max_steps
 
 int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
                           void* d_workspace, uint64_t workspace_bytes) {
-    // n is the y extent of the expansion / canonical-form launches (one row of workgroups per instance): at most 65535
-    if (!out || n == 0 || n > 65535 || max_steps == 0 || !d_workspace || n_buffers == 0 || n_buffers > BLSW_MAX_BUFFERS || !options || msg_len > 65535)
-        return BLSW_ERR_ARG;
-    // consumer mode is late materialisation out of the staging: a direct-mode engine (one step, one buffer) writes its witnesses in
-    // place while the chains run and could not honour a held output
-    if (options->consumer_mode > 1 || (options->consumer_mode == 1 && max_steps == 1 && n_buffers == 1)) return BLSW_ERR_ARG;
-    if (options->pairing_mode > 1 || options->g2_mode > 1 || (options->g2_mode == 1 && options->pairing_mode != 0) || options->expand_store > 3 ||
-        options->prio_mode > 2 || options->group_ramp > 1 || options->latency_mode > 4 || options->output_form > 1 || options->chain_variant > 2 || options->cofactor_mode > 2 || (options->expand_variant & 0xff) > 13 || (options->expand_variant >> 9) || options->n_keys > 65535 ||
-        (options->n_keys && options->g2_mode) || options->n_pairs > 4096)
-        return BLSW_ERR_ARG;
-    // N+1-pair product (options.n_pairs = K > 1): a staged engine with the default kernel modes; its expansion launch has one row of
-    // workgroups per (instance, pair)
-    if (options->n_pairs > 1 && (options->n_keys || options->pairing_mode || options->g2_mode || !(max_steps > 1 || n_buffers > 1) || n * options->n_pairs > 65535))
-        return BLSW_ERR_ARG;
-    // ParametersVar allocated as witnesses: the single-key circuit with the six-lane pairing kernel (k_pairing_team_pv)
-    if (options->params_mode > 1 || (options->params_mode && (options->n_keys || options->n_pairs > 1 || options->pairing_mode))) return BLSW_ERR_ARG;
-    // PublicKeyVar / SignatureVar allocated as public inputs: the single-key circuit with Constant parameters and the one-lane G2 kernels
-    if (options->pk_mode > 1 || options->sig_mode > 1 ||
-        ((options->pk_mode || options->sig_mode) && (options->n_keys || options->n_pairs > 1 || options->params_mode || options->g2_mode)))
-        return BLSW_ERR_ARG;
+    if (!out || !d_workspace) return BLSW_ERR_ARG;
+    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BLSW_ERR_NO_DEVICE;
@@ -681,7 +651,7 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     if (dev >= ndev) return BLSW_ERR_ARG;
     DeviceGuard guard(dev);
     uint64_t need = 0;
-    if (blsw_engine_workspace_bytes_ex(n, msg_len, max_steps, n_buffers, options, &need)) return BLSW_ERR_ARG;
+    blsw_engine_workspace_bytes_ex(n, msg_len, max_steps, n_buffers, options, &need);  // cannot fail: the options have been checked
     if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
     // Scratch guard. ROCr backs a queue's scratch for full-device occupancy: stack bytes per lane x 64 lanes x wave slots
     // (CUs x 32), per queue that runs the kernel. The single-lane pairing kernel (9.7 KB of stack) on four or more group
@@ -795,7 +765,7 @@ int blsw_engine_destroy(blsw_engine_t* e) {
     if (!e) return BLSW_ERR_ARG;
     DeviceGuard guard(e->device);
     hipDeviceSynchronize();
-    if (group_trace_on()) group_trace_dump();
+    group_trace_dump(e);
     engine_free(e);
     return BLSW_OK;
 }
@@ -924,17 +894,13 @@ int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t
     const Workspace w = carve(nullptr, e->n * K, e->L, true, e->modes, e->n);
     const CompactForm cf = compact_form(e->n, w, K);
     const char* src = reinterpret_cast<const char*>(d_compact);
-    if (K > 1) {
-        ExpandArgs xm = {reinterpret_cast<const uint32_t*>(src), w.sha_words, 0, e->L.sha_bits, e->L.off_expand, d_witness, witness_stride, K, e->L.stride_hash, 0, (int)e->opt.output_form};
-        launch_expand(e->opt.expand_variant, e->opt.expand_store, e->opt.place_lds, st, xm, (unsigned)(e->n * K));
+    ExpandArgs xa = {reinterpret_cast<const uint32_t*>(src), w.sha_words, 0, e->L.sha_bits, e->L.off_expand, d_witness, witness_stride, K, K > 1 ? e->L.stride_hash : 0u, 0, (int)e->opt.output_form};
+    engine_expand(e, st, xa, (unsigned)(e->n * K));
+    if (K > 1)
         launch_place_multi(e, st, w, reinterpret_cast<const Fp*>(src + cf.off_staging), 0, reinterpret_cast<const Fp*>(src + cf.off_inst), 0, cf.inst_tile_w,
                            reinterpret_cast<const Fp*>(src + cf.off_pair), d_witness, witness_stride);
-        if (e->opt.output_form) launch_canonical(e, st, d_witness, witness_stride);
-        return hip_ok(hipGetLastError(), "expand compact");
-    }
-    ExpandArgs xa = {reinterpret_cast<const uint32_t*>(src), w.sha_words, 0, e->L.sha_bits, e->L.off_expand, d_witness, witness_stride, 1u, 0u, 0, (int)e->opt.output_form};
-    launch_expand(e->opt.expand_variant, e->opt.expand_store, e->opt.place_lds, st, xa, (unsigned)e->n);
-    launch_place(e, st, reinterpret_cast<const Fp*>(src + cf.off_staging), reinterpret_cast<const Fp*>(src + cf.off_pair), w.split_row, 0, d_witness, witness_stride);
+    else
+        launch_place(e, st, reinterpret_cast<const Fp*>(src + cf.off_staging), reinterpret_cast<const Fp*>(src + cf.off_pair), w.split_row, 0, d_witness, witness_stride);
     if (e->opt.output_form) launch_canonical(e, st, d_witness, witness_stride);
     return hip_ok(hipGetLastError(), "expand compact");
 }
@@ -1034,46 +1000,49 @@ static int put_desc(StepDesc* d_desc, const StepDesc& h, hipStream_t st) {
     if (hip_ok(hipMemcpyAsync(d_desc, &h, sizeof(h), hipMemcpyHostToDevice, st), "memcpy")) return BLSW_ERR_HIP;
     return hip_ok(hipStreamSynchronize(st), "sync");  // `h` is a stack object
 }
-static Group direct_group(uint64_t n, uint32_t K, uint32_t msg_len, const blsw_layout_t& L, StepDesc* d_desc, const Workspace& ws) {
-    Group g;
-    g.N = n * K;
-    g.n = (uint32_t)n;
-    g.K = K;
-    g.msg_len = msg_len;
-    g.desc = d_desc;
-    g.L = L;
-    g.LS = L;
-    g.ws = ws;
-    g.chain_prio = 0;
-    g.canonical = 0;
-    return g;
+// Prologue of the value-only direct calls (hash to G2, verify, sign) on the device that owns `st` (the caller holds its DeviceGuard): n lanes carved
+// at d_workspace + off_ws, the one-step descriptor (the messages) at the workspace head
+static int direct_values_group(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, void* d_workspace, uint64_t workspace_bytes, uint64_t off_ws, hipStream_t st,
+                               Group* g) {
+    blsw_layout_t L;
+    make_layout(msg_len, &L);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    const Workspace ws = carve(base + off_ws, n, L, false, DEFAULT_MODES);
+    if (off_ws + ws.total_bytes > workspace_bytes) return BLSW_ERR_WORKSPACE;
+    StepDesc* d_desc = reinterpret_cast<StepDesc*>(base);
+    *g = make_group(1, n, 1, msg_len, d_desc, L, ws);
+    StepDesc h = {nullptr, nullptr, d_msg, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return put_desc(d_desc, h, st);
+}
+static uint64_t direct_values_bytes(uint64_t n, uint32_t msg_len, uint64_t off_ws) {
+    blsw_layout_t L;
+    make_layout(msg_len, &L);
+    return off_ws + carve(nullptr, n, L, false, DEFAULT_MODES).total_bytes;
+}
+// the value-only hash to G2 of the group's messages, into its workspace
+static void launch_values_hash(const Group& g, hipStream_t st) {
+    const unsigned g1 = (unsigned)((g.N + 63) / 64), g2 = (unsigned)((2 * g.N + 63) / 64);
+    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
+    hipLaunchKernelGGL(k_map_values, dim3(g2), dim3(64), 0, st, g);
+    hipLaunchKernelGGL(k_cofactor_values, dim3(g1), dim3(64), 0, st, g);
 }
 
 int blsw_hash_to_g2_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
                           void* stream_) {
     if ((!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_out_affine || msg_len > 65535) return BLSW_ERR_ARG;
-    blsw_layout_t L;
-    make_layout(msg_len, &L);
-    // the step descriptor lives at the head of the workspace
-    StepDesc* d_desc = reinterpret_cast<StepDesc*>(d_workspace);
-    Workspace ws = carve(reinterpret_cast<char*>(d_workspace) + 256, n, L, false, DEFAULT_MODES);
-    if (ws.total_bytes + 256 > workspace_bytes) return BLSW_ERR_WORKSPACE;
-    Group g = direct_group(n, 1, msg_len, L, d_desc, ws);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
-    StepDesc h = {nullptr, nullptr, d_msg, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    if (int rc = put_desc(d_desc, h, st)) return rc;
-    const unsigned g1 = (unsigned)((n + 63) / 64), g2 = (unsigned)((2 * n + 63) / 64);
-    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_map_values, dim3(g2), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_cofactor_values, dim3(g1), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_h_to_affine, dim3(g1), dim3(64), 0, st, n, g.ws, d_out_affine);
+    Group g;
+    if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, 256, st, &g)) return rc;
+    launch_values_hash(g, st);
+    hipLaunchKernelGGL(k_h_to_affine, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, g.ws, d_out_affine);
     return hip_ok(hipGetLastError(), "launch");
 }
 // BLS::verify (bls.rs:427-458) for a batch of compressed (pk, sig) and messages, as VALUES (no circuit): decode with the endomorphism subgroup checks,
 // the value-only hash to G2, projective line coefficients and a two-pair Miller loop + final exponentiation on the six-lane team (vpairing.hpp).
 // d_result[i] = 1 iff both points decode to non-identity subgroup points and e(-g1, sig) e(pk, H(m)) = 1; d_status [n][2] as blsw_decode_batch.
-static uint64_t verify_workspace(uint64_t n, const blsw_layout_t& L, uint64_t* off_pk, uint64_t* off_sig, uint64_t* off_ls, uint64_t* off_lh, uint64_t* off_ws) {
+// Workspace: the step descriptor, the decoded points, the line coefficients of sig and H(m), then the hash's carve (at the offset returned).
+static uint64_t verify_offsets(uint64_t n, uint64_t* off_pk, uint64_t* off_sig, uint64_t* off_ls, uint64_t* off_lh) {
     uint64_t o = 256;  // the step descriptor
     *off_pk = o;
     o = align_up(o + n * 96, 256);
@@ -1082,39 +1051,28 @@ static uint64_t verify_workspace(uint64_t n, const blsw_layout_t& L, uint64_t* o
     *off_ls = o;
     o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * n * sizeof(Fp), 256);
     *off_lh = o;
-    o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * n * sizeof(Fp), 256);
-    *off_ws = o;
-    return o + carve(nullptr, n, L, false, DEFAULT_MODES).total_bytes;
+    return align_up(o + (uint64_t)BLSW_VLINE_ROWS * n * sizeof(Fp), 256);
 }
 int blsw_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes) {
     if (!bytes || n == 0 || n > 0x7fffffffu || msg_len > 65535) return BLSW_ERR_ARG;
-    blsw_layout_t L;
-    make_layout(msg_len, &L);
-    uint64_t a, b, c, d, e;
-    *bytes = verify_workspace(n, L, &a, &b, &c, &d, &e);
+    uint64_t a, b, c, d;
+    *bytes = direct_values_bytes(n, msg_len, verify_offsets(n, &a, &b, &c, &d));
     return BLSW_OK;
 }
 int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result, int32_t* d_status,
                       void* d_workspace, uint64_t workspace_bytes, void* stream_) {
     if (!d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_result || !d_status || !d_workspace || msg_len > 65535) return BLSW_ERR_ARG;
-    blsw_layout_t L;
-    make_layout(msg_len, &L);
-    uint64_t off_pk, off_sig, off_ls, off_lh, off_ws;
-    if (verify_workspace(n, L, &off_pk, &off_sig, &off_ls, &off_lh, &off_ws) > workspace_bytes) return BLSW_ERR_WORKSPACE;
+    uint64_t off_pk, off_sig, off_ls, off_lh;
+    const uint64_t off_ws = verify_offsets(n, &off_pk, &off_sig, &off_ls, &off_lh);
     char* base = reinterpret_cast<char*>(d_workspace);
-    StepDesc* d_desc = reinterpret_cast<StepDesc*>(base);
     uint64_t* pk_xy = reinterpret_cast<uint64_t*>(base + off_pk);
     uint64_t* sig_xy = reinterpret_cast<uint64_t*>(base + off_sig);
-    Group g = direct_group(n, 1, msg_len, L, d_desc, carve(base + off_ws, n, L, false, DEFAULT_MODES));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));
-    StepDesc h = {nullptr, nullptr, d_msg, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    if (int rc = put_desc(d_desc, h, st)) return rc;
-    const unsigned g1 = (unsigned)((n + 63) / 64), g2 = (unsigned)((2 * n + 63) / 64);
-    hipLaunchKernelGGL(k_decode, dim3(g2), dim3(64), 0, st, d_pk48, d_sig96, n, pk_xy, sig_xy, d_status);
-    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_map_values, dim3(g2), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_cofactor_values, dim3(g1), dim3(64), 0, st, g);
+    Group g;
+    if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
+    hipLaunchKernelGGL(k_decode, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, d_pk48, d_sig96, n, pk_xy, sig_xy, d_status);
+    launch_values_hash(g, st);
     launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + off_ls), reinterpret_cast<Fp*>(base + off_lh), d_status, d_result, st);
     return hip_ok(hipGetLastError(), "launch");
 }
@@ -1122,21 +1080,12 @@ int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8
 int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
                     uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
     if (!d_sk32_le || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_status || msg_len > 65535) return BLSW_ERR_ARG;
-    blsw_layout_t L;
-    make_layout(msg_len, &L);
-    StepDesc* d_desc = reinterpret_cast<StepDesc*>(d_workspace);
-    Workspace ws = carve(reinterpret_cast<char*>(d_workspace) + 256, n, L, false, DEFAULT_MODES);
-    if (ws.total_bytes + 256 > workspace_bytes) return BLSW_ERR_WORKSPACE;
-    Group g = direct_group(n, 1, msg_len, L, d_desc, ws);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
-    StepDesc h = {nullptr, nullptr, d_msg, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    if (int rc = put_desc(d_desc, h, st)) return rc;
-    const unsigned g1 = (unsigned)((n + 63) / 64), g2 = (unsigned)((2 * n + 63) / 64);
-    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_map_values, dim3(g2), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_cofactor_values, dim3(g1), dim3(64), 0, st, g);
-    hipLaunchKernelGGL(k_sign, dim3(g2), dim3(64), 0, st, n, g.ws, d_sk32_le, d_sig96, d_sig_xy, d_pk48, d_pk_xy, d_status);
+    Group g;
+    if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, 256, st, &g)) return rc;
+    launch_values_hash(g, st);
+    hipLaunchKernelGGL(k_sign, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, n, g.ws, d_sk32_le, d_sig96, d_sig_xy, d_pk48, d_pk_xy, d_status);
     return hip_ok(hipGetLastError(), "launch");
 }
 int blsw_layout_aggregate(uint32_t msg_len, uint32_t n_keys, blsw_layout_t* out) {
@@ -1173,7 +1122,7 @@ int blsw_aggregate_verify_batch(const uint64_t* d_pks_xy, const uint8_t* d_bitma
     char* base = reinterpret_cast<char*>(d_workspace);
     StepDesc* d_desc = reinterpret_cast<StepDesc*>(base + off_desc);
     Fp* keyproj = reinterpret_cast<Fp*>(base + off_keyproj);
-    Group g = direct_group(n, 1, msg_len, L, d_desc, carve(base + off_ws, n, L, false, DEFAULT_MODES));
+    Group g = make_group(1, n, 1, msg_len, d_desc, L, carve(base + off_ws, n, L, false, DEFAULT_MODES));
     const ChainKernels ck = chain_kernels(true);  // direct mode: few waves, latency-bound
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
@@ -1209,7 +1158,7 @@ int blsw_layout_multi(uint32_t msg_len, uint32_t n_pairs, blsw_layout_t* out) {
 int blsw_verify_multi_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_pairs, uint64_t* bytes) {
     blsw_layout_t L;
     if (!bytes || n == 0 || blsw_layout_multi(msg_len, n_pairs, &L)) return BLSW_ERR_ARG;
-    *bytes = 256 + carve(nullptr, n * n_pairs, L, false, DEFAULT_MODES, n).total_bytes + miller_par_bytes(n, n_pairs, BLSW_MILLER_CHUNK_DEFAULT);
+    *bytes = 256 + carve(nullptr, n * n_pairs, L, false, DEFAULT_MODES, n).total_bytes + miller_par_bytes(n, n_pairs);
     return BLSW_OK;
 }
 int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint64_t* d_sig_xy, uint64_t n,
@@ -1222,9 +1171,9 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
     StepDesc* d_desc = reinterpret_cast<StepDesc*>(d_workspace);
     Workspace ws = carve(reinterpret_cast<char*>(d_workspace) + 256, NP, L, false, DEFAULT_MODES, n);
     const bool par = n_pairs >= BLSW_MILLER_PAR_MIN_PAIRS;  // pairs in parallel (miller_par.hpp); few pairs: one team walks the chain
-    if (ws.total_bytes + 256 + (par ? miller_par_bytes(n, n_pairs, BLSW_MILLER_CHUNK_DEFAULT) : 0) > workspace_bytes) return BLSW_ERR_WORKSPACE;
-    Group gp = direct_group(n, n_pairs, msg_len, L, d_desc, ws);  // per-pair work: N = n * n_pairs lanes
-    Group gs = direct_group(n, 1, msg_len, L, d_desc, ws);        // per-signature work: N = n lanes
+    if (ws.total_bytes + 256 + (par ? miller_par_bytes(n, n_pairs) : 0) > workspace_bytes) return BLSW_ERR_WORKSPACE;
+    Group gp = make_group(1, n, n_pairs, msg_len, d_desc, L, ws);  // per-pair work: N = n * n_pairs lanes
+    Group gs = make_group(1, n, 1, msg_len, d_desc, L, ws);        // per-signature work: N = n lanes
     const ChainKernels ck = chain_kernels(true);                  // direct mode: few waves, latency-bound
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     const int dev = stream_device(st);  // the device that owns `stream`
@@ -1233,31 +1182,12 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
     if (int rc = put_desc(d_desc, h, st)) return rc;
     const unsigned p1 = (unsigned)((NP + 63) / 64);
     // fork: the signature's allocation + prepare (one lane per instance: 57 ms of latency) and the keys' allocation run beside the
-    // hash-to-G2 chains of the pairs; join in front of the Miller product. The two side streams and three events are created once
-    // per host thread and device and kept (an event is re-recorded per call; a wait refers to the record that preceded it).
-    struct Side {
-        int device = -1;
-        hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-        hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-        bool ok = false;
-    };
-    static thread_local std::map<int, Side> sides;  // per host thread and device ordinal (the device that owns `stream`)
-    Side& sd = sides[dev];
-    if (sd.device != dev) {
-        sd.device = dev;
-        sd.ok = hipStreamCreateWithFlags(&sd.aux[0], hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&sd.aux[1], hipStreamNonBlocking) == hipSuccess &&
-                hipStreamCreateWithFlags(&sd.aux[2], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&sd.ev_fork, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&sd.ev_join[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&sd.ev_join[1], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&sd.ev_join[2], hipEventDisableTiming) == hipSuccess;
-    }
-    const bool forked = sd.ok;
-    hipEvent_t ev_fork = sd.ev_fork;
-    hipEvent_t* ev_join = sd.ev_join;
-    hipStream_t s_sig = forked ? sd.aux[0] : st, s_keys = forked ? sd.aux[1] : st;
-    if (forked) {
-        hipEventRecord(ev_fork, st);  // the descriptor copy
-        hipStreamWaitEvent(s_sig, ev_fork, 0);
-        hipStreamWaitEvent(s_keys, ev_fork, 0);
+    // hash-to-G2 chains of the pairs; join in front of the Miller product (the thread's side streams: side_lanes)
+    SideLanes* sd = side_lanes(dev);
+    hipStream_t s_sig = sd ? sd->aux[0] : st, s_keys = sd ? sd->aux[1] : st, s_exp = sd ? sd->aux[2] : st;
+    if (sd) {
+        hipEventRecord(sd->ev_fork, st);  // the descriptor copy
+        for (hipStream_t q : sd->aux) hipStreamWaitEvent(q, sd->ev_fork, 0);
     }
     const Latency lat = {ws.cofv != nullptr, ws.cofv != nullptr};  // a small direct call is latency-bound: quads, values-first cofactor chain
     launch_g2_alloc(ck, lat, gs, s_sig);
@@ -1265,8 +1195,6 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
     hipLaunchKernelGGL(ck.g1, dim3(p1), dim3(64), 0, s_keys, gp);
     // the SHA witness bits and their expansion (92 % of the output bytes) need only the messages: their own stream, beside the curve
     // chains; the chains start from the value-only hash_to_field
-    hipStream_t s_exp = forked ? sd.aux[2] : st;
-    if (forked) hipStreamWaitEvent(s_exp, ev_fork, 0);
     if (d_witness) {
         hipLaunchKernelGGL(ck.sha, dim3(p1), dim3(64), 0, s_exp, gp, 1, 0);
         // blockIdx.y = flat (instance, pair); grid.y <= 65535: several launches for larger batches
@@ -1281,38 +1209,16 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
     launch_map(ck, lat, gp, st);
     launch_cofactor_direct(ck, lat, gp, st, dev);
     launch_prepare(ck, lat, gp, 0, st);
-    if (forked) {
-        hipEventRecord(ev_join[0], s_sig);
-        hipEventRecord(ev_join[1], s_keys);
-        hipEventRecord(ev_join[2], s_exp);
-        hipStreamWaitEvent(st, ev_join[0], 0);
-        hipStreamWaitEvent(st, ev_join[1], 0);
-        hipStreamWaitEvent(st, ev_join[2], 0);
+    if (sd) {
+        for (int i = 0; i < 3; i++) hipEventRecord(sd->ev_join[i], sd->aux[i]);
+        for (hipEvent_t ev : sd->ev_join) hipStreamWaitEvent(st, ev, 0);
     }
     if (!par) {
         hipLaunchKernelGGL(k_pairing_team_multi, dim3((unsigned)((n + BLSW_TEAMS_PER_WAVE - 1) / BLSW_TEAMS_PER_WAVE)), dim3(64), 0, st, gs, n_pairs, NP);
         return hip_ok(hipGetLastError(), "launch");
     }
-    MillerParArgs ma;
-    ma.K = n_pairs;
-    ma.B = BLSW_MILLER_CHUNK_DEFAULT;
-    ma.C = (n_pairs + ma.B - 1) / ma.B;
-    ma.n_h = NP;
-    ma.spine_lane = 0;
-    {
-        char* p = reinterpret_cast<char*>(d_workspace) + align_up(256 + ws.total_bytes, 256);
-        auto take = [&](uint64_t items) {
-            Fp* r = reinterpret_cast<Fp*>(p);
-            p += align_up(items * 12 * sizeof(Fp), 256);
-            return r;
-        };
-        ma.cprod = take(n * 68 * ma.C);
-        ma.q = take(n * 68 * ma.C);
-        ma.t = take(n * 68);
-        ma.f1 = take(n * 68);
-        ma.ffinal = take(n);
-    }
-    launch_miller_par(gs, ma, st, forked ? s_sig : nullptr, ev_fork, ev_join[0]);
+    const MillerParArgs ma = carve_miller_par(reinterpret_cast<char*>(d_workspace) + align_up(256 + ws.total_bytes, 256), n, n_pairs);
+    launch_miller_par(gs, ma, st, sd ? s_sig : nullptr, sd ? sd->ev_fork : nullptr, sd ? sd->ev_join[0] : nullptr);
     return hip_ok(hipGetLastError(), "launch");
 }
 
@@ -1346,9 +1252,7 @@ int blsw_aggregate_points_batch(uint32_t group, const uint8_t* d_in, uint32_t k,
 }
 int blsw_hash_to_g2_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes) {
     if (!bytes || n == 0 || msg_len > 65535) return BLSW_ERR_ARG;
-    blsw_layout_t L;
-    make_layout(msg_len, &L);
-    *bytes = carve(nullptr, n, L, false, DEFAULT_MODES).total_bytes + 256;
+    *bytes = direct_values_bytes(n, msg_len, 256);
     return BLSW_OK;
 }
 

@@ -439,9 +439,29 @@ struct MillerParArgs {
     uint64_t n_h;      // n * K: lanes of the per-pair launches (where the pairs' line coefficients / prepared keys live)
     uint32_t spine_lane;  // 1: the single-lane spine kernel (k_miller_m2; the statement shared with the host harness) instead of the team kernel
 };
-inline uint64_t miller_par_bytes(uint64_t n, uint32_t K, uint32_t B) {
-    const uint64_t C = (K + B - 1) / B;
-    return (2 * n * 68 * C + 2 * n * 68 + n) * 12 * sizeof(Fp) + 5 * 256;
+#define BLSW_MILLER_CHUNK_DEFAULT 12  // pairs per lane of the engine's pair-parallel Miller product
+// The value stores of n instances of K pairs at `base`, each 256-byte aligned; *bytes (miller_par_bytes) is the size the same rows are given
+inline MillerParArgs carve_miller_par(char* base, uint64_t n, uint32_t K, uint64_t* bytes = nullptr) {
+    MillerParArgs a = {};
+    a.K = K;
+    a.B = BLSW_MILLER_CHUNK_DEFAULT;
+    a.C = (K + a.B - 1) / a.B;
+    a.n_h = n * K;
+    Fp** const store[5] = {&a.cprod, &a.q, &a.t, &a.f1, &a.ffinal};
+    const uint64_t rows[5] = {n * 68 * a.C, n * 68 * a.C, n * 68, n * 68, n};
+    uint64_t off = 0, need = 0;
+    for (int i = 0; i < 5; i++) {
+        *store[i] = reinterpret_cast<Fp*>(base + off);
+        off += align_up(rows[i] * 12 * sizeof(Fp), 256);
+        need += rows[i] * 12 * sizeof(Fp) + 256;
+    }
+    if (bytes) *bytes = need;
+    return a;
+}
+inline uint64_t miller_par_bytes(uint64_t n, uint32_t K) {
+    uint64_t bytes = 0;
+    carve_miller_par(nullptr, n, K, &bytes);
+    return bytes;
 }
 void launch_miller_par(const Group& gs, const MillerParArgs& a, hipStream_t st, hipStream_t side, hipEvent_t ev_spine, hipEvent_t ev_side);
 // Placement of the N+1-pair product's staged rows (k_stream.hip): up to six runs of consecutive staging rows of a lane, each going to
@@ -487,6 +507,18 @@ struct CofactorSide {
     hipEvent_t ev_seg[BLSW_COFV_NSEG], ev_pts[BLSW_COFV_NSEG], ev_acc[3], ev_join;
 };
 #define BLSW_COFV_EVENTS (2 * BLSW_COFV_NSEG + 4)
+// a CofactorSide of four streams and an array of BLSW_COFV_EVENTS events: ev_seg, ev_pts, ev_acc, ev_join in that order
+inline CofactorSide cofactor_side(hipStream_t side, hipStream_t pts, hipStream_t acc0, hipStream_t acc1, const hipEvent_t ev[BLSW_COFV_EVENTS]) {
+    CofactorSide cs;
+    cs.side = side;
+    cs.pts = pts;
+    cs.acc[0] = acc0;
+    cs.acc[1] = acc1;
+    for (int i = 0; i < BLSW_COFV_NSEG; i++) cs.ev_seg[i] = ev[i], cs.ev_pts[i] = ev[BLSW_COFV_NSEG + i];
+    for (int i = 0; i < 3; i++) cs.ev_acc[i] = ev[2 * BLSW_COFV_NSEG + i];
+    cs.ev_join = ev[2 * BLSW_COFV_NSEG + 3];
+    return cs;
+}
 inline uint64_t cofv_total_adds() {
     constexpr CofvPlan plan = cofv_plan();
     return (uint64_t)plan.n_adds[0] + plan.n_adds[1] + plan.n_adds[2];

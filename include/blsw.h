@@ -178,9 +178,11 @@ typedef struct {
                               blsw_engine_submit_io, which also writes instance_assignment. Single-key circuit with Constant parameters only. */
     uint32_t sig_mode;     /* SignatureVar allocation (src/constraints.rs:234-249): 0 (default) Witness, 1 Input; as pk_mode; not with g2_mode 1 */
 } blsw_engine_options_t;
-/* the defaults (pure: the library reads no environment variable; measurement scripts set the fields they want to vary) */
+/* the defaults (pure: measurement scripts set the fields they want to vary). The one environment variable the library reads is the
+ * diagnostic BLSW_TRACE_GROUP=1: an engine prints its launch groups' stage times to stderr at blsw_engine_destroy. */
 int blsw_engine_options_default(blsw_engine_options_t* out);
 int blsw_engine_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, uint64_t* bytes);
+/* BLSW_ERR_ARG for every argument and option set blsw_engine_create_ex refuses with BLSW_ERR_ARG before it looks at the device */
 int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options, uint64_t* bytes);
 /* blsw_engine_create = blsw_engine_create_ex with blsw_engine_options_default. Returns BLSW_ERR_SCRATCH (nothing is
  * allocated) when pairing_mode 1 is combined with so many group buffers that the runtime's per-queue scratch
