@@ -17,10 +17,25 @@ SOURCES = ["engine.hip", "k_bench.hip", "k_cofactor.hip", "k_cofv.hip", "k_g1.hi
            "k_sign.hip", "k_stream.hip", "k_team.hip", "k_values.hip"]
 HOST_SOURCES = ["r1cs.cpp"]  # host-only C++: compiled by g++, linked into the same library
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h")))
-# the one-instance-per-lane chain units are compiled a second time with their programs inlined (kernels *_inl: kcommon.hpp)
-DUAL = ["k_sha.hip", "k_g1.hip", "k_g2.hip", "k_map.hip", "k_cofactor.hip", "k_prepare.hip"]
-# the units whose chains have a latency compilation: one chain on the four lanes of a quad (kernels *_q: kcommon.hpp, fp.hpp)
-QUAD = ["k_map.hip", "k_cofv.hip", "k_prepare.hip", "k_g2.hip"]
+# The one-instance-per-lane chain units: source -> (register policy of the grouped-engine compilation, the unit's other compilations, why).
+# The grouped compilation keeps the plain kernel names and gets -DBLSW_CHAIN_<policy>; kcommon.hpp turns that into BLSW_INLINE_CHAINS and BLSW_CHAIN_ATTR:
+#   W2       programs inlined into the kernel, two waves per SIMD (<= 256 registers)
+#   OUTLINE  programs out of line (BLSW_FN functions): ~410 registers, one wave per SIMD with ~100 registers left to the streaming kernels on it
+#   FULL     programs inlined, the whole register file
+# Other compilations: "inl" = direct mode (kernels *_inl, -DBLSW_KVARIANT_INL: inlined, the whole register file), "q" = latency (kernels *_q,
+# -DBLSW_KVARIANT_QUAD: inlined, one chain on the four lanes of a quad, fp.hpp). An A/B build of another policy edits an entry in a scratch copy.
+_SHORT_W2 = "the short chains: +4 % on the 20-step job at two waves, neutral in the steady state (profiles/r03_ab_chain_builds.txt)"
+CHAIN_UNITS = {
+    "k_sha.hip": ("W2", ("inl",), _SHORT_W2),
+    "k_g1.hip": ("W2", ("inl",), _SHORT_W2),
+    "k_g2.hip": ("OUTLINE", ("inl", "q"), "inlined it takes the whole file and the expansion starves; at two waves it spills 590 registers into its hot loop "
+                 "(profiles/r03_ab_chain_builds.txt)"),
+    "k_map.hip": ("W2", ("inl", "q"), _SHORT_W2),
+    "k_cofactor.hip": ("OUTLINE", ("inl",), "inlined it takes the whole file and the expansion starves; at two waves it spills 2 400 registers into its hot loop "
+                       "(profiles/r03_ab_chain_builds.txt)"),
+    "k_prepare.hip": ("W2", ("inl", "q"), _SHORT_W2),
+    "k_cofv.hip": ("FULL", ("q",), "the serial phases and the join: at two waves the join spills 2 000 registers into its additions"),
+}
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas"]
 
@@ -82,13 +97,13 @@ def _tool_version(tool):
 
 def build_tag(defines=()):
     """Key of the object cache: everything that shapes an object besides its source and headers — the compilers (path and --version: the
-    ROCm release), the flags, the defines and the list of doubly compiled units. "std" names the shipped configuration's logs
+    ROCm release), the flags, the defines and the compilations of the chain units (CHAIN_UNITS without the reasons). "std" names the shipped configuration's logs
     (resource_table); the objects carry the hash."""
     hipcc, cxx = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), os.environ.get("CXX", "g++")
     memo = (hipcc, cxx, tuple(defines))
     if memo in _TAGS:  # one pair of compiler processes per Python process, not per call
         return _TAGS[memo]
-    key = "\n".join([hipcc, _tool_version(hipcc), cxx, _tool_version(cxx), " ".join(HIP_FLAGS), " ".join(HOST_FLAGS), " ".join(defines), " ".join(DUAL), " ".join(QUAD)])
+    key = "\n".join([hipcc, _tool_version(hipcc), cxx, _tool_version(cxx), " ".join(HIP_FLAGS), " ".join(HOST_FLAGS), " ".join(defines), repr([(src, u[:2]) for src, u in sorted(CHAIN_UNITS.items())])])
     _TAGS[memo] = hashlib.sha1(key.encode()).hexdigest()[:8]
     return _TAGS[memo]
 
@@ -110,9 +125,10 @@ def build(force=False, verbose=False, out=None, defines=()):
     hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     hdr_time = max(hdr_time, os.path.getmtime(os.path.join(HERE, "..", "include", "blsw.h")))
     jobs, objs = [], []
-    units = [(src, ()) for src in HOST_SOURCES + SOURCES] + [(src, ("-DBLSW_KVARIANT_INL",)) for src in DUAL] + [(src, ("-DBLSW_KVARIANT_QUAD",)) for src in QUAD]
-    for src, extra in units:
-        suffix = "_inl" if "-DBLSW_KVARIANT_INL" in extra else ("_q" if extra else "")
+    units = [(src, "", ["-DBLSW_CHAIN_" + CHAIN_UNITS[src][0]] if src in CHAIN_UNITS else []) for src in HOST_SOURCES + SOURCES]
+    for c, define in (("inl", "-DBLSW_KVARIANT_INL"), ("q", "-DBLSW_KVARIANT_QUAD")):
+        units += [(src, "_" + c, [define]) for src, u in CHAIN_UNITS.items() if c in u[1]]
+    for src, suffix, extra in units:
         obj = os.path.join(OBJ, "%s%s.%s.o" % (os.path.splitext(src)[0], suffix, tag))
         objs.append(obj)
         path = os.path.join(CSRC, src)
@@ -128,7 +144,8 @@ def build(force=False, verbose=False, out=None, defines=()):
         print("compiling %d units" % len(jobs), file=sys.stderr)
     with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as ex:
         list(ex.map(_compile, jobs))
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out or OUT] + objs, cwd=CSRC)
+    # -z defs: a kernel the launch code names but no compilation defines fails the link, not the first load of the library
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", out or OUT] + objs, cwd=CSRC)
     open((out or OUT) + ".tag", "w").write(tag + "\n")
     return out or OUT
 

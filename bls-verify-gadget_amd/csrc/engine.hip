@@ -130,7 +130,7 @@ struct blsw_engine {
     uint32_t refs[BLSW_MAX_CONSUMED];       // consumer mode: accepted steps that will be materialised into this output (slot reserved at submit)
     uint32_t ramp_pos = 0;                  // options.group_ramp: launch groups since creation / the last flush (group sizes 2, 4, 8, ... max_steps)
     bool staged = false;  // false: direct mode (max_steps == 1, no staging; witnesses written in place by the chains)
-    bool chains_inlined = false;  // which compilation of the chain kernels (options.chain_variant; kcommon.hpp: BLSW_K)
+    bool chains_inlined = false;  // which compilation of the chain kernels (options.chain_variant; kcommon.hpp: chain_kernels)
     uint32_t cofactor_mode = 0;  // clear_cofactor2 with its three chunks on three lanes: 0 by group size, 1 never, 2 always (options.cofactor_mode)
     std::vector<GroupTrace> trace;  // BLSW_TRACE_GROUP
 };
@@ -396,7 +396,7 @@ static int launch_group(blsw_engine* e) {
     // Which kernels. A SMALL group (at most BLSW_LATENCY_MAX_LANES lanes) that finds the engine's chains idle starts a pipeline: nothing of this engine
     // runs beside it, and its latency — one wave's instruction stream, whatever the group's size — is what a consumer waits for before the first
     // tensors exist. Such a group takes the latency kernels (options.latency_mode 0): map / prepare / G2 allocation on quads and the cofactor chain
-    // values first (kcommon.hpp: Latency). "Idle" is the state of the other group buffers' chains, not a count of groups since the last flush.
+    // values first (kcommon.hpp: chain_kernels). "Idle" is the state of the other group buffers' chains, not a count of groups since the last flush.
     // (Letting the second small group of a starting pipeline take them too was measured: 56-57 k against 58-60 k instances/s for an 8 192-instance
     // shard in groups of 4 — two latency groups at once contend for the SIMDs the first one needs.)
     bool idle = true;
@@ -404,27 +404,27 @@ static int launch_group(blsw_engine* e) {
         if (k != e->cur && e->buf[k].used && hipEventQuery(e->buf[k].ev_chains) != hipSuccess) idle = false;
     const bool small = g.ws.cofv != nullptr;  // staged or direct mode (a direct-mode engine is one small group at a time: always latency-bound)
     const uint32_t lm = e->opt.latency_mode;
-    Latency lat = {false, false};
-    if (small && (lm >= 2 || (lm == 0 && idle))) lat = {lm != 3, lm != 4};
+    bool quad = false, vf = false;
+    if (small && (lm >= 2 || (lm == 0 && idle))) quad = lm != 3, vf = lm != 4;
+    const bool lat_any = quad || vf;
     // with the latency kernels off, such a group takes the inlined compilation of the chain kernels (options.chain_variant 0)
     const bool cold_small = e->opt.chain_variant == 0 && small && idle;
-    const ChainKernels ck = chain_kernels(e->chains_inlined || cold_small);
+    const ChainKernels ck = chain_kernels(e->chains_inlined || cold_small, quad);
     const bool chunked = e->cofactor_mode == 2 || (e->cofactor_mode == 0 && g.N <= BLSW_COFACTOR_CHUNKED_MAX_LANES);
     // values-first cofactor chain: its per-doubling / per-addition witness phases go to the aux stream, behind the aux chains (enqueued below)
     // ... and the pipelines of its chunks run beside the doubling chain on the buffer's main stream (the segments' points) and the engine's sha and
     // place streams (the addition chains): streams with nothing to do while a cold group's chains run (its SHA bits are enqueued before; placement
     // starts after the chains)
     const CofactorSide cof_side = cofactor_side(b.st[1], b.st[0], e->place, e->sha, b.ev_cof);
-    const bool cof_deferred = lat.vf && g.ws.cofv != nullptr;
+    const bool cof_deferred = vf && g.ws.cofv != nullptr;
     // the waves of a latency group's critical path (hash-to-G2, prepare(H), pairing) raise their priority: the streams beside them — the first
     // expansions, the next group's chains, this group's aux chains — have slack, they have none
     Group gm = g;
-    if (lat.quad || lat.vf) gm.chain_prio = 1;
+    if (lat_any) gm.chain_prio = 1;
     // The main path of a latency group runs on the engine's HIGH-priority latency stream: a pipe of the command processor hands its dispatcher to the
     // highest-priority queue that has a kernel ready, so beside an expansion (high-priority stream, 246 144 workgroups) a kernel launched on a
     // normal-priority stream waits until the expansion has been dispatched to its end (BLSW_TRACE_GROUP: prepare(H) 13 ms instead of 1.8). The
     // buffer's own main stream carries the points of the cofactor segments instead.
-    const bool lat_any = lat.quad || lat.vf;
     hipStream_t st = lat_any ? e->lat : b.st[0];
     // inputs of every step are ready once its submitting stream reached the point of the submit
     for (uint32_t s = 0; s < steps; s++) hipStreamWaitEvent(st, b.ev_in[s], 0);
@@ -449,16 +449,16 @@ static int launch_group(blsw_engine* e) {
     // main, first part: the hash-to-G2 critical path (per pair)
     group_trace_mark(trace, 0, st);
     hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, gm);
-    launch_map(ck, lat, gm, st);
+    launch_map(ck, gm, st);
     group_trace_mark(trace, 1, st);
-    launch_cofactor(ck, lat, chunked, gm, st, &cof_side);
+    launch_cofactor(ck, vf, chunked, gm, st, &cof_side);
     group_trace_mark(trace, 2, st);
-    launch_prepare(ck, lat, gm, 0, st);
+    launch_prepare(ck, vf, gm, 0, st);
     group_trace_mark(trace, 3, st);
     // aux: prepare_g2(sig) and the keys' allocation + prepare_g1 — what the pairing waits for (ev_aux) — then the signature's allocation chain, which
     // only the end of the group waits for (ev_side): the longest aux kernel no longer delays the pairing of a latency-bound group
     hipStream_t sb = b.st[1];
-    launch_prepare(ck, lat, gs, 1, sb);
+    launch_prepare(ck, vf, gs, 1, sb);
     if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
         hipLaunchKernelGGL(ck.agg_keys, dim3((unsigned)((g.N * e->L.n_keys + 63) / 64)), dim3(64), 0, sb, g, g.ws.keyproj);
         hipLaunchKernelGGL(ck.agg_sum, dim3(g1), dim3(64), 0, sb, g, (const Fp*)g.ws.keyproj);
@@ -470,8 +470,8 @@ static int launch_group(blsw_engine* e) {
     } else if (e->modes.g2_team)
         hipLaunchKernelGGL(k_g2_alloc_team, dim3(gt), dim3(64), 0, sb, g);
     else
-        launch_g2_alloc(ck, lat, gs, sb);
-    if (cof_deferred) launch_cofactor_witness(lat, g, cof_side);
+        launch_g2_alloc(ck, gs, sb);
+    if (cof_deferred) launch_cofactor_witness(ck, g, cof_side);
     // main, second part: the pairing
     hipStreamWaitEvent(st, b.ev_aux, 0);
     group_trace_mark(trace, 4, st);
@@ -526,16 +526,16 @@ static SideLanes* side_lanes(int dev) {
     return l.ok ? &l : nullptr;
 }
 // launch_cofactor of a direct call on `st`, with its pipelines on the thread's side streams; `st` has waited for all of it on return
-static void launch_cofactor_direct(const ChainKernels& ck, Latency lat, const Group& g, hipStream_t st, int dev) {
+static void launch_cofactor_direct(const ChainKernels& ck, bool vf, const Group& g, hipStream_t st, int dev) {
     const bool chunked = g.N <= BLSW_COFACTOR_CHUNKED_MAX_LANES;
-    SideLanes* d = (lat.vf && g.ws.cofv) ? side_lanes(dev) : nullptr;
+    SideLanes* d = (vf && g.ws.cofv) ? side_lanes(dev) : nullptr;
     if (!d) {
-        launch_cofactor(ck, lat, chunked, g, st);
+        launch_cofactor(ck, vf, chunked, g, st);
         return;
     }
     const CofactorSide cs = cofactor_side(d->cof[0], d->cof[1], d->cof[2], d->cof[3], d->ev_cof);
-    launch_cofactor(ck, lat, chunked, g, st, &cs);
-    launch_cofactor_witness(lat, g, cs);
+    launch_cofactor(ck, vf, chunked, g, st, &cs);
+    launch_cofactor_witness(ck, g, cs);
     hipEventRecord(d->ev_cof[BLSW_COFV_EVENTS], cs.side);
     hipStreamWaitEvent(st, d->ev_cof[BLSW_COFV_EVENTS], 0);
 }
@@ -1123,7 +1123,9 @@ int blsw_aggregate_verify_batch(const uint64_t* d_pks_xy, const uint8_t* d_bitma
     StepDesc* d_desc = reinterpret_cast<StepDesc*>(base + off_desc);
     Fp* keyproj = reinterpret_cast<Fp*>(base + off_keyproj);
     Group g = make_group(1, n, 1, msg_len, d_desc, L, carve(base + off_ws, n, L, false, DEFAULT_MODES));
-    const ChainKernels ck = chain_kernels(true);  // direct mode: few waves, latency-bound
+    // direct mode: few waves, latency-bound; a small call also takes the latency kernels (quads, values-first cofactor and prepare chains)
+    const bool small = g.ws.cofv != nullptr;
+    const ChainKernels ck = chain_kernels(true, small);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
     StepDesc h = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, d_pks_xy, d_bitmap, d_count};
@@ -1131,17 +1133,16 @@ int blsw_aggregate_verify_batch(const uint64_t* d_pks_xy, const uint8_t* d_bitma
     const unsigned g1 = (unsigned)((n + 63) / 64), gk = (unsigned)((n * n_keys + 63) / 64);
     hipLaunchKernelGGL(ck.agg_keys, dim3(gk), dim3(64), 0, st, g, keyproj);
     hipLaunchKernelGGL(ck.agg_sum, dim3(g1), dim3(64), 0, st, g, (const Fp*)keyproj);
-    const Latency lat = {g.ws.cofv != nullptr, g.ws.cofv != nullptr};  // a small direct call is latency-bound: quads, values-first cofactor chain
-    launch_g2_alloc(ck, lat, g, st);
-    launch_prepare(ck, lat, g, 1, st);
+    launch_g2_alloc(ck, g, st);
+    launch_prepare(ck, small, g, 1, st);
     hipLaunchKernelGGL(ck.sha, dim3(g1), dim3(64), 0, st, g, d_witness ? 1 : 0, 1);
     if (d_witness) {
         ExpandArgs xa = {g.ws.bits, g.ws.sha_words, 0, g.L.sha_bits, g.L.off_expand, d_witness, witness_stride, 1u, 0u, 0};
         launch_expand(BLSW_DEFAULT_EXPAND_VARIANT, 0, 0, st, xa, (unsigned)n);
     }
-    launch_map(ck, lat, g, st);
-    launch_cofactor_direct(ck, lat, g, st, stream_device(st));
-    launch_prepare(ck, lat, g, 0, st);
+    launch_map(ck, g, st);
+    launch_cofactor_direct(ck, small, g, st, stream_device(st));
+    launch_prepare(ck, small, g, 0, st);
     launch_pairing(g, DEFAULT_MODES, st);
     return hip_ok(hipGetLastError(), "launch");
 }
@@ -1174,7 +1175,9 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
     if (ws.total_bytes + 256 + (par ? miller_par_bytes(n, n_pairs) : 0) > workspace_bytes) return BLSW_ERR_WORKSPACE;
     Group gp = make_group(1, n, n_pairs, msg_len, d_desc, L, ws);  // per-pair work: N = n * n_pairs lanes
     Group gs = make_group(1, n, 1, msg_len, d_desc, L, ws);        // per-signature work: N = n lanes
-    const ChainKernels ck = chain_kernels(true);                  // direct mode: few waves, latency-bound
+    // direct mode: few waves, latency-bound; a small call also takes the latency kernels (quads, values-first cofactor and prepare chains)
+    const bool small = ws.cofv != nullptr;
+    const ChainKernels ck = chain_kernels(true, small);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     const int dev = stream_device(st);  // the device that owns `stream`
     DeviceGuard guard(dev);
@@ -1189,9 +1192,8 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
         hipEventRecord(sd->ev_fork, st);  // the descriptor copy
         for (hipStream_t q : sd->aux) hipStreamWaitEvent(q, sd->ev_fork, 0);
     }
-    const Latency lat = {ws.cofv != nullptr, ws.cofv != nullptr};  // a small direct call is latency-bound: quads, values-first cofactor chain
-    launch_g2_alloc(ck, lat, gs, s_sig);
-    launch_prepare(ck, lat, gs, 1, s_sig);
+    launch_g2_alloc(ck, gs, s_sig);
+    launch_prepare(ck, small, gs, 1, s_sig);
     hipLaunchKernelGGL(ck.g1, dim3(p1), dim3(64), 0, s_keys, gp);
     // the SHA witness bits and their expansion (92 % of the output bytes) need only the messages: their own stream, beside the curve
     // chains; the chains start from the value-only hash_to_field
@@ -1206,9 +1208,9 @@ int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uin
         }
     }
     hipLaunchKernelGGL(k_sha_values, dim3(p1), dim3(64), 0, st, gp);
-    launch_map(ck, lat, gp, st);
-    launch_cofactor_direct(ck, lat, gp, st, dev);
-    launch_prepare(ck, lat, gp, 0, st);
+    launch_map(ck, gp, st);
+    launch_cofactor_direct(ck, small, gp, st, dev);
+    launch_prepare(ck, small, gp, 0, st);
     if (sd) {
         for (int i = 0; i < 3; i++) hipEventRecord(sd->ev_join[i], sd->aux[i]);
         for (hipEvent_t ev : sd->ev_join) hipStreamWaitEvent(st, ev, 0);

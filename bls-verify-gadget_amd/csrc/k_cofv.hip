@@ -9,11 +9,8 @@
 //   k_cofv_add_w   phase 4, one lane per addition: its eight witnesses                          }
 //   k_cofv_join    phase 5, one lane per pair: folds the chunks (the statements of k_cofactor_join)
 // kcommon.hpp's launch_cofactor pipelines the segments over four streams: phases 1b / 2a / 3 of a segment run beside phase 1 of the next ones.
-// Two compilations (build.py): this one (programs inlined; the parallel phases at two waves per SIMD) and the latency compilation (-DBLSW_KVARIANT_QUAD:
-// k_cofv_chain_q, k_cofv_bwd_q, k_cofv_acc_q, k_cofv_az_q — the serial phases on the four lanes of a quad, fp.hpp).
-#define BLSW_INLINE_CHAINS 1
+// A chain unit: its compilations and the register policy of its grouped compilation are its entry in build.py's CHAIN_UNITS.
 #include "kcommon.hpp"
-#define BLSW_CHAIN_ATTR  // the serial phases and the join: the whole register file (at 256 registers the join spills 2 000 into its additions)
 
 namespace blsw {
 

@@ -1,17 +1,6 @@
 // libblsw.so, one translation unit per kernel family (see kcommon.hpp, build.py).
-// Two compilations (build.py, kcommon.hpp: BLSW_K). Grouped-engine compilation of THIS unit: programs inlined into the kernel and
-// two waves per SIMD (<= 256 registers) — measured +4 % on the 20-step job, neutral in the steady state (profiles/r03_ab_chain_builds.txt);
-// -DBLSW_OUTLINE_MAP restores the out-of-line build for A/B runs. Direct-mode compilation (*_inl): inlined, the whole register file.
-// Latency compilation (*_q, -DBLSW_KVARIANT_QUAD): inlined, one chain on the four lanes of a quad (fp.hpp: quads).
-#if defined(BLSW_KVARIANT_INL) || defined(BLSW_KVARIANT_QUAD) || !defined(BLSW_OUTLINE_MAP)
-#define BLSW_INLINE_CHAINS 1
-#endif
+// A chain unit: its compilations and the register policy of its grouped compilation are its entry in build.py's CHAIN_UNITS.
 #include "kcommon.hpp"
-#if !defined(BLSW_KVARIANT_INL) && !defined(BLSW_KVARIANT_QUAD) && !defined(BLSW_OUTLINE_MAP)
-#define BLSW_CHAIN_ATTR BLSW_ATTR_W2
-#else
-#define BLSW_CHAIN_ATTR
-#endif
 
 namespace blsw {
 

@@ -5,8 +5,40 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#ifdef BLSW_KVARIANT_QUAD  // the latency compilation of a chain unit: four lanes per item (fp.hpp: quads)
+// The compilations of the one-instance-per-lane chain units (build.py: CHAIN_UNITS, which says which unit has which and why). Before chains.hpp:
+// fp.hpp's BLSW_FN reads BLSW_INLINE_CHAINS (the programs inlined into the kernel, so that the kernel's register budget governs all of them).
+//   k_map      grouped engine: the unit's register policy, -DBLSW_CHAIN_W2 (inlined, two waves per SIMD), -DBLSW_CHAIN_OUTLINE (the programs out of
+//              line: 410-420 registers per kernel, which leaves room for a few waves of the streaming kernels on the same SIMD — what the grouped
+//              engine wants beside its HBM-bound expansion / placement) or -DBLSW_CHAIN_FULL (inlined, the whole register file)
+//   k_map_inl  (-DBLSW_KVARIANT_INL) inlined, the whole 512-register file, 0.1-0.7 KB of stack instead of 1.2-3.9 KB out of line (no argument /
+//              callee-saved traffic through scratch): 1.2-3.5x shorter under HBM load (k_map 32.8 -> 9.2 ms, k_g1 22 -> 8.5 ms in
+//              blsw_verify_multi_batch) — what the direct-mode entries want (few waves, latency-bound)
+//   k_map_q    (-DBLSW_KVARIANT_QUAD) inlined, and every chain on the four lanes of a quad with the independent Fp products of an Fp2 operation
+//              on different lanes (fp.hpp: quads, gadgets.hpp): the latency compilation, for small launch groups that start a pipeline
+// A unit that is no chain unit defines none of these: its programs are out of line.
+#define BLSW_ATTR_W2 __attribute__((amdgpu_waves_per_eu(2, 2)))  // register budget of a kernel: two waves per SIMD
+#if defined(BLSW_KVARIANT_QUAD)
 #define BLSW_QUAD 1
+#define BLSW_INLINE_CHAINS 1
+#define BLSW_CHAIN_ATTR
+#define BLSW_K(name) name##_q
+#define BLSW_LPI 4u  // lanes per item (instance, pair, chunk) of this compilation's kernels
+#elif defined(BLSW_KVARIANT_INL)
+#define BLSW_INLINE_CHAINS 1
+#define BLSW_CHAIN_ATTR
+#define BLSW_K(name) name##_inl
+#define BLSW_LPI 1u
+#else
+#if defined(BLSW_CHAIN_W2) || defined(BLSW_CHAIN_FULL)
+#define BLSW_INLINE_CHAINS 1
+#endif
+#ifdef BLSW_CHAIN_W2
+#define BLSW_CHAIN_ATTR BLSW_ATTR_W2
+#else
+#define BLSW_CHAIN_ATTR
+#endif
+#define BLSW_K(name) name
+#define BLSW_LPI 1u
 #endif
 #include "chains.hpp"
 #include "cofactor_vf.hpp"
@@ -15,11 +47,6 @@
 
 namespace blsw {
 
-#ifdef BLSW_KVARIANT_QUAD
-#define BLSW_LPI 4u  // lanes per item (instance, pair, chunk) of this compilation's kernels
-#else
-#define BLSW_LPI 1u
-#endif
 // index of this thread's item, and whether it is the lane of its item that writes the item's outputs (values are identical on the lanes of a quad)
 __device__ __forceinline__ uint64_t item_index() { return ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / BLSW_LPI; }
 __device__ __forceinline__ bool item_leader() { return BLSW_LPI == 1u || (threadIdx.x & (BLSW_LPI - 1u)) == 0u; }
@@ -338,23 +365,6 @@ struct ExpandArgs {
 #define BLSW_EXPAND_RESIDENT_WGS 512u  // expand_variant 13 (k_stream.hip): two 384-thread workgroups per compute unit
 
 #define BLSW_TEAMS_PER_WAVE 10
-#define BLSW_ATTR_W2 __attribute__((amdgpu_waves_per_eu(2, 2)))  // register budget of a kernel: two waves per SIMD
-// The one-instance-per-lane chain units (k_sha, k_g1, k_g2, k_map, k_cofactor, k_prepare) are compiled TWICE (build.py):
-//   k_map      the chain programs out of line (BLSW_FN functions): 410-420 registers per kernel, which leaves room for a few waves of the
-//              streaming kernels on the same SIMD — what the grouped engine wants beside its HBM-bound expansion / placement
-//   k_map_inl  (-DBLSW_KVARIANT_INL) the programs inlined into the kernel: the whole 512-register file, 0.1-0.7 KB of stack instead of
-//              1.2-3.9 KB (no argument / callee-saved traffic through scratch): 1.2-3.5x shorter under HBM load (k_map 32.8 -> 9.2 ms,
-//              k_g1 22 -> 8.5 ms in blsw_verify_multi_batch) — what the direct-mode entries want (few waves, latency-bound)
-//   k_map_q    (-DBLSW_KVARIANT_QUAD) inlined, and every chain on the four lanes of a quad with the independent Fp products of an Fp2 operation
-//              on different lanes (fp.hpp, gadgets.hpp): the latency compilation, for small launch groups that start a pipeline
-#if defined(BLSW_KVARIANT_QUAD)
-#define BLSW_K(name) name##_q
-#elif defined(BLSW_KVARIANT_INL)
-#define BLSW_K(name) name##_inl
-#else
-#define BLSW_K(name) name
-#endif
-
 #ifndef BLSW_PLACE_ITERS
 #define BLSW_PLACE_ITERS 8
 #endif
@@ -364,54 +374,40 @@ struct ExpandArgs {
 #define BLSW_DIGEST_A 0x85EBCA6Bu
 
 // ---------------------------------------------------------------- kernels (defined in k_*.hip, launched by engine.hip)
-__global__ void k_sha(Group g, int want_bits, int write_u);
-__global__ void k_sha_inl(Group g, int want_bits, int write_u);
+// A chain kernel's compilations (build.py: CHAIN_UNITS): grouped engine (name), direct mode (name_inl), latency (name_q)
+#define BLSW_CHAIN_I(name, params) __global__ void name params; __global__ void name##_inl params;
+#define BLSW_CHAIN_Q(name, params) __global__ void name params; __global__ void name##_q params;
+#define BLSW_CHAIN_IQ(name, params) BLSW_CHAIN_I(name, params) __global__ void name##_q params;
+BLSW_CHAIN_I(k_sha, (Group g, int want_bits, int write_u))
+BLSW_CHAIN_I(k_g1, (Group g))
+BLSW_CHAIN_I(k_agg_keys, (Group g, Fp* keyproj))
+BLSW_CHAIN_I(k_agg_sum, (Group g, const Fp* keyproj))
+BLSW_CHAIN_I(k_cofactor, (Group g))
+BLSW_CHAIN_I(k_cofactor_chunk, (Group g))
+BLSW_CHAIN_I(k_cofactor_join, (Group g))
+BLSW_CHAIN_IQ(k_g2_alloc, (Group g))
+BLSW_CHAIN_IQ(k_map, (Group g))
+BLSW_CHAIN_IQ(k_prepare, (Group g, int which))
+// values-first prepare chains (prepare_vf.hpp; k_prepare.hip): the serial value phase per point, then one lane per step
+BLSW_CHAIN_Q(k_prepv_chain, (Group g, int which))
+__global__ void k_prepv_step_w(Group g, int which);
+// values-first cofactor chain (cofactor_vf.hpp; k_cofv.hip): serial value phases (one lane or one quad per item), parallel witness phases, join
+BLSW_CHAIN_Q(k_cofv_chain, (Group g, int s))
+BLSW_CHAIN_Q(k_cofv_bwd, (Group g, int s))
+BLSW_CHAIN_Q(k_cofv_acc, (Group g, int s))
+BLSW_CHAIN_Q(k_cofv_az, (Group g))
+__global__ void k_cofv_aff(Group g, uint32_t lo, uint32_t cnt);
+__global__ void k_cofv_dbl_w(Group g);
+__global__ void k_cofv_add_w(Group g);
+__global__ void k_cofv_join(Group g);
 __global__ void k_sha_values(Group g);
+__global__ void k_map_values(Group g);
+__global__ void k_cofactor_values(Group g);
 __global__ void k_place_field(const Fp* __restrict__ staging, const Fp* __restrict__ pair, uint64_t first, uint32_t off_expand, uint32_t sha_bits,
                               uint32_t staging_rows, uint32_t split_row, uint64_t* __restrict__ d_witness, uint64_t stride, uint32_t n_inst, uint32_t moved_lo,
                               uint32_t moved_len, uint32_t moved_at);
 __global__ void k_canonical_rows(uint64_t* __restrict__ d_witness, uint64_t stride, uint32_t off_expand, uint32_t sha_bits, uint32_t rows, uint32_t K, uint32_t stride_hash);
 __global__ void k_digest(const uint64_t* __restrict__ w, uint64_t stride, uint64_t n_words, uint64_t* __restrict__ digest);
-__global__ void k_g1(Group g);
-__global__ void k_g1_inl(Group g);
-__global__ void k_agg_keys(Group g, Fp* keyproj);
-__global__ void k_agg_keys_inl(Group g, Fp* keyproj);
-__global__ void k_agg_sum(Group g, const Fp* keyproj);
-__global__ void k_agg_sum_inl(Group g, const Fp* keyproj);
-__global__ void k_g2_alloc(Group g);
-__global__ void k_g2_alloc_inl(Group g);
-__global__ void k_map(Group g);
-__global__ void k_map_inl(Group g);
-__global__ void k_cofactor(Group g);
-__global__ void k_cofactor_inl(Group g);
-__global__ void k_cofactor_chunk(Group g);
-__global__ void k_cofactor_chunk_inl(Group g);
-__global__ void k_cofactor_join(Group g);
-__global__ void k_cofactor_join_inl(Group g);
-__global__ void k_map_q(Group g);
-__global__ void k_prepare_q(Group g, int which);
-__global__ void k_g2_alloc_q(Group g);
-// values-first prepare chains (prepare_vf.hpp; k_prepare.hip): the serial value phase per point, then one lane per step
-__global__ void k_prepv_chain(Group g, int which);
-__global__ void k_prepv_chain_q(Group g, int which);
-__global__ void k_prepv_step_w(Group g, int which);
-// values-first cofactor chain (cofactor_vf.hpp; k_cofv.hip): serial value phases (one lane or one quad per item), parallel witness phases, join
-__global__ void k_cofv_chain(Group g, int s);
-__global__ void k_cofv_chain_q(Group g, int s);
-__global__ void k_cofv_bwd(Group g, int s);
-__global__ void k_cofv_bwd_q(Group g, int s);
-__global__ void k_cofv_acc(Group g, int s);
-__global__ void k_cofv_acc_q(Group g, int s);
-__global__ void k_cofv_az(Group g);
-__global__ void k_cofv_az_q(Group g);
-__global__ void k_cofv_aff(Group g, uint32_t lo, uint32_t cnt);
-__global__ void k_cofv_dbl_w(Group g);
-__global__ void k_cofv_add_w(Group g);
-__global__ void k_cofv_join(Group g);
-__global__ void k_map_values(Group g);
-__global__ void k_cofactor_values(Group g);
-__global__ void k_prepare(Group g, int which);
-__global__ void k_prepare_inl(Group g, int which);
 __global__ void k_pairing(Group g);
 __global__ void k_pairing_team(Group g);
 __global__ void k_pairing_team_pv(Group g);
@@ -474,28 +470,39 @@ struct PlaceRuns {
 __global__ void k_place_runs(const Fp* __restrict__ tiles, uint64_t first, uint32_t rows, PlaceRuns runs, uint64_t* __restrict__ d_witness, uint64_t stride, uint32_t n_y,
                              uint32_t K, uint32_t tile_w);
 __global__ void k_place_rows(const Fp* __restrict__ rows, uint32_t n_rows, uint32_t dst_off, uint64_t* __restrict__ d_witness, uint64_t stride);
-// the two compilations of the chain units as one table
+// The chain kernels a launch group or a direct call starts, in the compilations it picked (chain_kernels). The quad-capable ones — G2 allocation,
+// map, prepare and the serial phases of the values-first chains (prepare_vf.hpp, cofactor_vf.hpp) — run `lpi` lanes per item, the others one.
 struct ChainKernels {
     void (*sha)(Group, int, int);
     void (*g1)(Group);
     void (*agg_keys)(Group, Fp*);
     void (*agg_sum)(Group, const Fp*);
-    void (*g2_alloc)(Group);
-    void (*map)(Group);
     void (*cofactor)(Group);
-    void (*prepare)(Group, int);
     void (*cofactor_chunk)(Group);  // the cofactor segment with its three chunks on three lanes, and the join (cofactor_par.hpp)
     void (*cofactor_join)(Group);
+    void (*g2_alloc)(Group);
+    void (*map)(Group);
+    void (*prepare)(Group, int);
+    void (*prepv_chain)(Group, int);
+    void (*cofv_chain)(Group, int);
+    void (*cofv_bwd)(Group, int);
+    void (*cofv_acc)(Group, int);
+    void (*cofv_az)(Group);
+    unsigned lpi;
 };
-inline ChainKernels chain_kernels(bool inlined) {
-    if (inlined) return {k_sha_inl, k_g1_inl, k_agg_keys_inl, k_agg_sum_inl, k_g2_alloc_inl, k_map_inl, k_cofactor_inl, k_prepare_inl, k_cofactor_chunk_inl, k_cofactor_join_inl};
-    return {k_sha, k_g1, k_agg_keys, k_agg_sum, k_g2_alloc, k_map, k_cofactor, k_prepare, k_cofactor_chunk, k_cofactor_join};
+// inlined: the direct-mode compilation (*_inl) instead of the grouped engine's; quad: the latency compilation (*_q, four lanes per item) of the
+// quad-capable kernels. The values-first phases have no direct-mode compilation: without quad they are the grouped one whatever `inlined` says.
+inline ChainKernels chain_kernels(bool inlined, bool quad) {
+#define BLSW_PICK_I(name) (inlined ? name##_inl : name)
+#define BLSW_PICK_Q(name) (quad ? name##_q : name)
+#define BLSW_PICK_IQ(name) (quad ? name##_q : BLSW_PICK_I(name))
+    return {BLSW_PICK_I(k_sha), BLSW_PICK_I(k_g1), BLSW_PICK_I(k_agg_keys), BLSW_PICK_I(k_agg_sum), BLSW_PICK_I(k_cofactor), BLSW_PICK_I(k_cofactor_chunk),
+            BLSW_PICK_I(k_cofactor_join), BLSW_PICK_IQ(k_g2_alloc), BLSW_PICK_IQ(k_map), BLSW_PICK_IQ(k_prepare), BLSW_PICK_Q(k_prepv_chain),
+            BLSW_PICK_Q(k_cofv_chain), BLSW_PICK_Q(k_cofv_bwd), BLSW_PICK_Q(k_cofv_acc), BLSW_PICK_Q(k_cofv_az), quad ? 4u : 1u};
+#undef BLSW_PICK_I
+#undef BLSW_PICK_Q
+#undef BLSW_PICK_IQ
 }
-// Latency forms of a launch group's chains (small groups: Workspace::cofv exists): `quad` = the *_q compilation of map / prepare / G2 allocation and
-// of the serial phases of the values-first cofactor chain (four lanes per item); `vf` = clear_cofactor2 values first (cofactor_vf.hpp)
-struct Latency {
-    bool quad, vf;
-};
 // clear_cofactor2 of N lanes on `st`: values first, chunked (three lanes per (pk, msg) pair + the join) or as one chain per lane.
 // Values first with side streams (CofactorSide): `st` carries the forward doubling chain in its segments and the last segment's tail. Beside it, as soon
 // as a segment's doublings are done (ev_seg): its inversion / affine points on pts, in segment order (ev_pts), and its part of its chunk's addition chain
@@ -523,68 +530,51 @@ inline uint64_t cofv_total_adds() {
     constexpr CofvPlan plan = cofv_plan();
     return (uint64_t)plan.n_adds[0] + plan.n_adds[1] + plan.n_adds[2];
 }
-inline void launch_cofv_chain(Latency lat, const Group& g, int s, hipStream_t q) {
-    if (lat.quad)
-        hipLaunchKernelGGL(k_cofv_chain_q, dim3(item_grid(g.N, 4)), dim3(64), 0, q, g, s);
-    else
-        hipLaunchKernelGGL(k_cofv_chain, dim3(item_grid(g.N, 1)), dim3(64), 0, q, g, s);
-}
 // phases 1b and 2a of segment s: 1 / Z of its points, then the points in affine form
-inline void launch_cofv_points(Latency lat, const Group& g, int s, hipStream_t q) {
+inline void launch_cofv_points(const ChainKernels& ck, const Group& g, int s, hipStream_t q) {
     constexpr CofvSeg seg = cofv_seg();
-    if (lat.quad)
-        hipLaunchKernelGGL(k_cofv_bwd_q, dim3(item_grid(g.N, 4)), dim3(64), 0, q, g, s);
-    else
-        hipLaunchKernelGGL(k_cofv_bwd, dim3(item_grid(g.N, 1)), dim3(64), 0, q, g, s);
+    hipLaunchKernelGGL(ck.cofv_bwd, dim3(item_grid(g.N, ck.lpi)), dim3(64), 0, q, g, s);
     const uint32_t lo = s == 0 ? 0 : seg.bnd[s] + 1u;
     const uint32_t hi = seg.bnd[s + 1] < BLSW_H_EFF_NBITS ? seg.bnd[s + 1] : BLSW_H_EFF_NBITS - 1;  // the last point of the chain is not an operand
     hipLaunchKernelGGL(k_cofv_aff, dim3(item_grid((uint64_t)(hi - lo + 1) * g.N, 1)), dim3(64), 0, q, g, lo, hi - lo + 1);
 }
-inline void launch_cofv_acc(Latency lat, const Group& g, int s, hipStream_t q) {
-    if (lat.quad)
-        hipLaunchKernelGGL(k_cofv_acc_q, dim3(item_grid(g.N, 4)), dim3(64), 0, q, g, s);
-    else
-        hipLaunchKernelGGL(k_cofv_acc, dim3(item_grid(g.N, 1)), dim3(64), 0, q, g, s);
-}
-inline void launch_cofv_witness_phases(Latency lat, const Group& g, hipStream_t q) {
+inline void launch_cofv_witness_phases(const ChainKernels& ck, const Group& g, hipStream_t q) {
     hipLaunchKernelGGL(k_cofv_dbl_w, dim3(item_grid((uint64_t)BLSW_H_EFF_NBITS * g.N, 1)), dim3(64), 0, q, g);
-    if (lat.quad)
-        hipLaunchKernelGGL(k_cofv_az_q, dim3(item_grid(3 * g.N, 4)), dim3(64), 0, q, g);
-    else
-        hipLaunchKernelGGL(k_cofv_az, dim3(item_grid(3 * g.N, 1)), dim3(64), 0, q, g);
+    hipLaunchKernelGGL(ck.cofv_az, dim3(item_grid(3 * g.N, ck.lpi)), dim3(64), 0, q, g);
     hipLaunchKernelGGL(k_cofv_add_w, dim3(item_grid(cofv_total_adds() * g.N, 1)), dim3(64), 0, q, g);
 }
-inline void launch_cofactor(const ChainKernels& ck, Latency lat, bool chunked, const Group& g, hipStream_t st, const CofactorSide* side = nullptr) {
-    const unsigned g1 = item_grid(g.N, 1), g3 = item_grid(3 * g.N, 1);
-    if (lat.vf && g.ws.cofv) {
+// vf: clear_cofactor2 values first (cofactor_vf.hpp), if the workspace has its scratch (small groups)
+inline void launch_cofactor(const ChainKernels& ck, bool vf, bool chunked, const Group& g, hipStream_t st, const CofactorSide* side = nullptr) {
+    const unsigned g1 = item_grid(g.N, 1), g3 = item_grid(3 * g.N, 1), gq = item_grid(g.N, ck.lpi);
+    if (vf && g.ws.cofv) {
         constexpr CofvSeg seg = cofv_seg();
         constexpr int last = BLSW_COFV_NSEG - 1;
         if (!side) {
             for (int s = 0; s <= last; s++) {
-                launch_cofv_chain(lat, g, s, st);
-                launch_cofv_points(lat, g, s, st);
-                launch_cofv_acc(lat, g, s, st);
+                hipLaunchKernelGGL(ck.cofv_chain, dim3(gq), dim3(64), 0, st, g, s);
+                launch_cofv_points(ck, g, s, st);
+                hipLaunchKernelGGL(ck.cofv_acc, dim3(gq), dim3(64), 0, st, g, s);
             }
             hipLaunchKernelGGL(k_cofv_join, dim3(g1), dim3(64), 0, st, g);
-            launch_cofv_witness_phases(lat, g, st);
+            launch_cofv_witness_phases(ck, g, st);
             return;
         }
         for (int s = 0; s <= last; s++) {
-            launch_cofv_chain(lat, g, s, st);
+            hipLaunchKernelGGL(ck.cofv_chain, dim3(gq), dim3(64), 0, st, g, s);
             hipEventRecord(side->ev_seg[s], st);
         }
         for (int s = 0; s < last; s++) {
             hipStreamWaitEvent(side->pts, side->ev_seg[s], 0);
-            launch_cofv_points(lat, g, s, side->pts);
+            launch_cofv_points(ck, g, s, side->pts);
             hipEventRecord(side->ev_pts[s], side->pts);
             hipStream_t q = side->acc[seg.chunk[s] == 1 ? 1 : 0];
             hipStreamWaitEvent(q, side->ev_pts[s], 0);
-            launch_cofv_acc(lat, g, s, q);
+            hipLaunchKernelGGL(ck.cofv_acc, dim3(gq), dim3(64), 0, q, g, s);
             if (seg.last(s) || s == last - 1) hipEventRecord(side->ev_acc[seg.chunk[s]], q);
         }
-        launch_cofv_points(lat, g, last, st);
+        launch_cofv_points(ck, g, last, st);
         hipStreamWaitEvent(st, side->ev_acc[2], 0);  // the chunk's additions before the last segment's
-        launch_cofv_acc(lat, g, last, st);
+        hipLaunchKernelGGL(ck.cofv_acc, dim3(gq), dim3(64), 0, st, g, last);
         hipStreamWaitEvent(st, side->ev_acc[0], 0);
         hipStreamWaitEvent(st, side->ev_acc[1], 0);
         hipLaunchKernelGGL(k_cofv_join, dim3(g1), dim3(64), 0, st, g);
@@ -597,34 +587,20 @@ inline void launch_cofactor(const ChainKernels& ck, Latency lat, bool chunked, c
     }
 }
 // the deferred witness phases of a values-first cofactor chain (launch_cofactor with side streams), enqueued on the side stream
-inline void launch_cofactor_witness(Latency lat, const Group& g, const CofactorSide& side) {
+inline void launch_cofactor_witness(const ChainKernels& ck, const Group& g, const CofactorSide& side) {
     hipStreamWaitEvent(side.side, side.ev_join, 0);
-    launch_cofv_witness_phases(lat, g, side.side);
+    launch_cofv_witness_phases(ck, g, side.side);
 }
-inline void launch_map(const ChainKernels& ck, Latency lat, const Group& g, hipStream_t st) {
-    if (lat.quad)
-        hipLaunchKernelGGL(k_map_q, dim3(item_grid(2 * g.N, 4)), dim3(64), 0, st, g);
-    else
-        hipLaunchKernelGGL(ck.map, dim3(item_grid(2 * g.N, 1)), dim3(64), 0, st, g);
-}
-inline void launch_prepare(const ChainKernels& ck, Latency lat, const Group& g, int which, hipStream_t st) {
-    if (lat.vf && g.ws.prepv_h) {
-        if (lat.quad)
-            hipLaunchKernelGGL(k_prepv_chain_q, dim3(item_grid(g.N, 4)), dim3(64), 0, st, g, which);
-        else
-            hipLaunchKernelGGL(k_prepv_chain, dim3(item_grid(g.N, 1)), dim3(64), 0, st, g, which);
+inline void launch_map(const ChainKernels& ck, const Group& g, hipStream_t st) { hipLaunchKernelGGL(ck.map, dim3(item_grid(2 * g.N, ck.lpi)), dim3(64), 0, st, g); }
+// vf: prepare_g2 values first (prepare_vf.hpp), if the workspace has its scratch (small groups)
+inline void launch_prepare(const ChainKernels& ck, bool vf, const Group& g, int which, hipStream_t st) {
+    if (vf && g.ws.prepv_h) {
+        hipLaunchKernelGGL(ck.prepv_chain, dim3(item_grid(g.N, ck.lpi)), dim3(64), 0, st, g, which);
         hipLaunchKernelGGL(k_prepv_step_w, dim3(item_grid((uint64_t)BLSW_PREPV_STEPS * g.N, 1)), dim3(64), 0, st, g, which);
-    } else if (lat.quad)
-        hipLaunchKernelGGL(k_prepare_q, dim3(item_grid(g.N, 4)), dim3(64), 0, st, g, which);
-    else
-        hipLaunchKernelGGL(ck.prepare, dim3(item_grid(g.N, 1)), dim3(64), 0, st, g, which);
+    } else
+        hipLaunchKernelGGL(ck.prepare, dim3(item_grid(g.N, ck.lpi)), dim3(64), 0, st, g, which);
 }
-inline void launch_g2_alloc(const ChainKernels& ck, Latency lat, const Group& g, hipStream_t st) {
-    if (lat.quad)
-        hipLaunchKernelGGL(k_g2_alloc_q, dim3(item_grid(g.N, 4)), dim3(64), 0, st, g);
-    else
-        hipLaunchKernelGGL(ck.g2_alloc, dim3(item_grid(g.N, 1)), dim3(64), 0, st, g);
-}
+inline void launch_g2_alloc(const ChainKernels& ck, const Group& g, hipStream_t st) { hipLaunchKernelGGL(ck.g2_alloc, dim3(item_grid(g.N, ck.lpi)), dim3(64), 0, st, g); }
 // host-side launch helpers that live next to their (templated) kernels
 void launch_expand(uint32_t variant, uint32_t store, unsigned lds, hipStream_t st, ExpandArgs a, unsigned n_y);
 void launch_pairing(const Group& g, const Modes& m, hipStream_t st);
