@@ -120,6 +120,12 @@ def lib():
         L.blsw_verify_batch.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
         L.blsw_microbench.argtypes = [ctypes.c_int, u32, u32, ctypes.POINTER(ctypes.c_double)]
         L.blsw_fill_rate.argtypes = [vp, u64, u32, ctypes.POINTER(ctypes.c_double)]
+        mi, mp = ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)
+        L.blsw_r1cs_device_bytes.argtypes = [mi, mp, ctypes.POINTER(u64)]
+        L.blsw_r1cs_create.argtypes = [ctypes.POINTER(vp), mi, mp, ctypes.c_int32, vp, u64, vp]
+        L.blsw_r1cs_destroy.argtypes = [vp]
+        L.blsw_r1cs_check.argtypes = [vp, vp, u64, vp, u64, u64, u32, vp, vp, vp]
+        L.blsw_r1cs_evaluate.argtypes = [vp, vp, u64, vp, u64, u64, u32, u64, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -129,7 +135,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_engine_output_consumed", "blsw_engine_compact_bytes", "blsw_engine_submit_compact", "blsw_engine_submit_aggregate_compact", "blsw_engine_expand_compact", "blsw_engine_expand_stats", "blsw_witness_digest", "blsw_hash_to_g2_workspace_bytes", "blsw_hash_to_g2_batch",
                     "blsw_decode_batch", "blsw_layout_aggregate", "blsw_aggregate_workspace_bytes", "blsw_aggregate_verify_batch", "blsw_layout_multi",
                     "blsw_verify_multi_workspace_bytes", "blsw_verify_multi_batch", "blsw_matrices_info", "blsw_matrices_fill", "blsw_sign_batch", "blsw_microbench", "blsw_fill_rate", "blsw_layout_io", "blsw_engine_submit_io", "blsw_verify_workspace_bytes", "blsw_verify_batch", "blsw_matrices_info_io", "blsw_matrices_fill_io",
-                    "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch"]
+                    "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch",
+                    "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -761,6 +768,135 @@ def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode
         raise BlswError("blsw_matrices_fill failed: %d" % rc)
     return {"n_constraints": info.n_constraints, "n_instance_vars": info.n_instance_vars, "n_witness": info.n_witness,
             "A": (rp[0], col[0], val[0]), "B": (rp[1], col[1], val[1]), "C": (rp[2], col[2], val[2])}
+
+
+def _matrices_struct(mats):
+    """(blsw_matrices_info_t, blsw_matrices_t) pointing into the numpy arrays of a matrices() dict (which must stay alive)"""
+    import numpy as np
+
+    info = blsw_matrices_info_t(mats["n_constraints"], mats["n_instance_vars"], mats["n_witness"])
+    m = blsw_matrices_t()
+    for k, name in enumerate("ABC"):
+        rp, col, val = mats[name]
+        assert rp.dtype == np.uint64 and col.dtype == np.uint32 and val.dtype == np.uint64 and rp.flags.c_contiguous and col.flags.c_contiguous and val.flags.c_contiguous
+        info.nnz[k] = col.shape[0]
+        m.row_ptr[k] = rp.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        m.col[k] = col.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        m.val[k] = val.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    return info, m
+
+
+def r1cs_device_bytes(mats):
+    """blsw_r1cs_device_bytes: bytes of the device encoding of a matrices() dict (validates it: BlswError on a malformed CSR)"""
+    info, m = _matrices_struct(mats)
+    b = ctypes.c_uint64(0)
+    rc = lib().blsw_r1cs_device_bytes(ctypes.byref(info), ctypes.byref(m), ctypes.byref(b))
+    if rc:
+        raise BlswError("blsw_r1cs_device_bytes failed: %d" % rc)
+    return b.value
+
+
+class ConstraintChecker:
+    """The constraint system of one circuit shape on the GPU (blsw_r1cs_*): arkworks' cs.is_satisfied() / cs.which_is_unsatisfied() and the
+    A z, B z, C z rows, for a batch of witness vectors at once. Arguments as matrices(). Inputs are the tensors WitnessEngine writes:
+    witness [n, >= n_witness, 6] int64 (a padded stride is honoured), instance [n, >= n_instance_vars, 6] (required when the circuit has
+    public inputs), form 0 = Montgomery, 1 = canonical (options.output_form). The encoded matrices live in a device tensor this object
+    owns; it is read-only after construction and recorded on every stream a call runs on."""
+
+    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None):
+        torch = _require_cuda()
+        self.torch = torch
+        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode)
+        self.n_constraints, self.n_instance_vars, self.n_witness = int(mats["n_constraints"]), int(mats["n_instance_vars"]), int(mats["n_witness"])
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device("cuda:%d" % torch.cuda.current_device())
+        info, m = _matrices_struct(mats)
+        b = ctypes.c_uint64(0)
+        rc = lib().blsw_r1cs_device_bytes(ctypes.byref(info), ctypes.byref(m), ctypes.byref(b))
+        if rc:
+            raise BlswError("blsw_r1cs_device_bytes failed: %d" % rc)
+        self.buffer = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        self._r = ctypes.c_void_p()
+        stream = torch.cuda.current_stream(self.device)
+        rc = lib().blsw_r1cs_create(ctypes.byref(self._r), ctypes.byref(info), ctypes.byref(m), self.device.index, self.buffer.data_ptr(), self.buffer.numel(),
+                                    stream.cuda_stream)
+        if rc:
+            self._r = None
+            raise BlswError("blsw_r1cs_create failed: %d" % rc)
+
+    @classmethod
+    def from_matrices(cls, mats, device=None):
+        """a checker of a matrices() dict (any shape, e.g. one already built for the host check)"""
+        return cls(device=device, _mats=mats)
+
+    def close(self):
+        if getattr(self, "_r", None):
+            lib().blsw_r1cs_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _io(self, witness, instance, stream):
+        """-> (n, instance pointer, instance stride, witness pointer, witness stride, stream) with the strides in field elements"""
+        torch = self.torch
+
+        def stride_of(t, need, what):
+            assert t.is_cuda and t.device == self.device and t.dtype == torch.int64 and t.dim() == 3 and t.shape[2] == 6, what
+            assert t.stride(2) == 1 and t.stride(1) == 6 and t.stride(0) % 6 == 0 and t.shape[1] >= need, "%s: [n, >= %d, 6] with rows of 6 contiguous limbs" % (what, need)
+            return t.stride(0) // 6
+
+        ws = stride_of(witness, self.n_witness, "witness")
+        n = witness.shape[0]
+        if instance is not None:
+            ist = stride_of(instance, self.n_instance_vars, "instance")
+            assert instance.shape[0] == n
+        elif self.n_instance_vars > 1:
+            raise BlswError("this circuit has %d public inputs: pass instance=" % (self.n_instance_vars - 1))
+        else:
+            ist = 0
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if s != torch.cuda.current_stream(self.device):
+            self.buffer.record_stream(s)
+        return n, instance.data_ptr() if instance is not None else None, ist, witness.data_ptr(), ws, s
+
+    def _check(self, witness, instance, form, stream, want_unreduced):
+        n, ip, ist, wp, ws, s = self._io(witness, instance, stream)
+        with self.torch.cuda.stream(s):
+            bad = self.torch.empty(n, dtype=self.torch.int64, device=self.device)
+            unr = self.torch.empty(n, dtype=self.torch.int64, device=self.device) if want_unreduced else None
+        rc = lib().blsw_r1cs_check(self._r, ip, ist, wp, ws, n, form, bad.data_ptr(), unr.data_ptr() if unr is not None else None, s.cuda_stream)
+        if rc:
+            raise BlswError("blsw_r1cs_check failed: %d" % rc)
+        return bad, unr
+
+    def which_is_unsatisfied(self, witness, instance=None, form=0, stream=None):
+        """int64 [n]: index of each instance's first unsatisfied constraint, -1 when it satisfies the system (asynchronous on `stream`)"""
+        return self._check(witness, instance, form, stream, False)[0]
+
+    def is_satisfied(self, witness, instance=None, form=0, stream=None):
+        """bool [n]"""
+        return self.which_is_unsatisfied(witness, instance, form, stream) < 0
+
+    def first_unreduced(self, witness, instance=None, form=0, stream=None):
+        """int64 [n]: each instance's first index k of z = [instance | witness] with z_k >= p, or -1"""
+        return self._check(witness, instance, form, stream, True)[1]
+
+    def evaluate(self, witness, instance=None, form=0, rows=None, stream=None):
+        """(az, bz, cz), int64 [n, count, 6] each: <A_j, z>, <B_j, z>, <C_j, z> for j in [begin, begin + count), reduced, in the input's form.
+        rows = (begin, count); default all rows."""
+        begin, count = rows if rows is not None else (0, self.n_constraints)
+        n, ip, ist, wp, ws, s = self._io(witness, instance, stream)
+        with self.torch.cuda.stream(s):
+            out = [self.torch.empty((n, count, 6), dtype=self.torch.int64, device=self.device) for _ in range(3)]
+        rc = lib().blsw_r1cs_evaluate(self._r, ip, ist, wp, ws, n, form, begin, count, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), s.cuda_stream)
+        if rc:
+            raise BlswError("blsw_r1cs_evaluate failed: %d" % rc)
+        return tuple(out)
 
 
 def layout_multi(msg_len, n_pairs):

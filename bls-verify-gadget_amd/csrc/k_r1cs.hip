@@ -1,0 +1,505 @@
+// Device R1CS evaluator (blsw_r1cs_*; include/blsw.h): <A_j, z> * <B_j, z> == <C_j, z> for n instances at a time, over the CSR matrices that
+// blsw_matrices_fill* emit, and the A z, B z, C z rows themselves.
+//
+// Encoding (host, blsw_r1cs_create): every entry is a u32 column and a u32 code, 8 bytes; the code's top two bits are its class:
+//   POS v / NEG v   coefficient +-v with 0 < v < 2^30 (the +-1 / +-2 of the boolean and SHA rows, the small constants of the curve rows)
+//   GEN idx         index into a table of the distinct Montgomery coefficients (powers of two from 2^30 up and the general constants)
+// Rows are cut into blocks of about equal work (entries weighted by class, plus the row's reductions); a wave walks one block.
+//
+// Kernel mapping: grid (row blocks / 4, groups of 64 instances), four waves per workgroup, lane = instance. All lanes walk the SAME
+// entries, so column, code and row pointers are wave-uniform and the class branch does not diverge; each lane gathers its own z[col].
+// A row's terms go into a 14-limb accumulator without reduction (+-v z is a 1 x 12-limb multiply, a table coefficient one Montgomery
+// product); the row ends with one Montgomery reduction per matrix (REDC of the 448-bit sum: X 2^-384 mod p) and the comparison
+//     REDC(A) * REDC(B) * K  ==  REDC(C)      (products in Montgomery form; K = R^2 for Montgomery input, R^3 for canonical input)
+// For Montgomery input (z = v R) REDC gives the canonical row value, for canonical input v R^-1; either way the two sides differ by
+// the same power of R. An empty A or B row skips the products.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <unordered_map>
+#include <vector>
+#include "../../include/blsw.h"
+#include "fp.hpp"
+
+using namespace blsw;
+
+namespace {
+
+constexpr uint32_t CLS_POS = 0u, CLS_NEG = 1u, CLS_GEN = 2u;
+constexpr uint32_t PAYLOAD_BITS = 30, PAYLOAD = (1u << PAYLOAD_BITS) - 1;
+constexpr int WAVES = 4;  // waves (row blocks) per workgroup
+// block cut: work units of an entry by class, of a row's reductions and comparison, and per block
+constexpr uint64_t W_ONE = 2, W_SMALL = 3, W_GEN = 10, W_ROW = 30, W_BLOCK = 16384;
+
+struct Enc {
+    const uint64_t* rp[3];   // row pointers [n_constraints + 1]
+    const uint2* ent[3];     // {column, code} [nnz]
+    const Fp* table;         // distinct Montgomery coefficients of class GEN
+    const uint64_t* blk;     // first row of every block [n_blocks + 1]
+};
+
+struct Args {
+    Enc e;
+    const uint64_t* inst;  // [n][inst_stride][6] or NULL (n_inst == 1)
+    const uint64_t* wit;   // [n][wit_stride][6]
+    uint64_t inst_stride, wit_stride, n;
+    uint32_t n_inst, blk_first, n_blk;
+    uint64_t row_lo, row_hi;  // rows evaluated (check: the whole matrix)
+    Fp one;                   // the constant one in the input's form (inst == NULL)
+    Fp k;                     // check: R^(3 - form); evaluate: R^2
+    uint64_t* bad;            // check: [n] first unsatisfied row (u64 max = none)
+    uint64_t* out[3];         // evaluate: [n][row_hi - row_lo][6]
+};
+
+struct Acc {
+    uint32_t l[14];
+};
+
+__device__ __forceinline__ void acc_add(Acc& x, const Fp& v) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) x.l[i] = addc32(x.l[i], v.l[i], c);
+    x.l[12] = addc32(x.l[12], 0, c);
+    x.l[13] += c;
+}
+// x += v * z, v < 2^30
+__device__ __forceinline__ void acc_add_small(Acc& x, const Fp& z, uint32_t v) {
+    uint32_t hi = 0, c = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const uint64_t t = (uint64_t)z.l[i] * v + hi;
+        hi = (uint32_t)(t >> 32);
+        x.l[i] = addc32(x.l[i], (uint32_t)t, c);
+    }
+    x.l[12] = addc32(x.l[12], hi, c);
+    x.l[13] += c;
+}
+// p - z (z <= p: a representative of -z below 2^381; 0 gives p, which the reduction absorbs)
+__device__ __forceinline__ Fp neg_raw(const Fp& z) {
+    constexpr uint32_t P[12] = BLSW_P_LIMBS;
+    Fp r;
+    uint32_t b = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) r.l[i] = subb32(P[i], z.l[i], b);
+    return r;
+}
+// Montgomery reduction of the 448-bit sum: X 2^-384 mod p. X < 2^443 (a row of < 2^32 terms below 2^411), so every partial value
+// (X + M p) / 2^(32 i) stays below 2^448 and the result below p + 2^59 < 2p.
+__device__ __noinline__ Fp redc14(Acc x) {
+    constexpr uint32_t P[12] = BLSW_P_LIMBS;
+    uint32_t* t = x.l;
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const uint32_t m = t[0] * BLSW_INV32;
+        uint64_t s = (uint64_t)m * P[0] + t[0];  // low word 0
+#pragma unroll
+        for (int j = 1; j < 12; j++) {
+            s = (uint64_t)m * P[j] + t[j] + (s >> 32);
+            t[j - 1] = (uint32_t)s;
+        }
+        s = (uint64_t)t[12] + (s >> 32);
+        t[11] = (uint32_t)s;
+        s = (uint64_t)t[13] + (s >> 32);
+        t[12] = (uint32_t)s;
+        t[13] = (uint32_t)(s >> 32);
+    }
+    Fp r;
+#pragma unroll
+    for (int i = 0; i < 12; i++) r.l[i] = t[i];
+    return fp_cond_sub_p(r, t[12]);
+}
+
+__device__ __forceinline__ Fp load_fp(const uint64_t* src) {
+    const uint4* q = reinterpret_cast<const uint4*>(src);
+    const uint4 a = q[0], b = q[1], c = q[2];
+    return Fp{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w}};
+}
+// z[col] of instance i (col is wave-uniform: so is the branch)
+__device__ __forceinline__ Fp load_z(const Args& a, uint64_t i, uint32_t col) {
+    if (col >= a.n_inst) return load_fp(a.wit + (i * a.wit_stride + (col - a.n_inst)) * 6);
+    if (a.inst) return load_fp(a.inst + (i * a.inst_stride + col) * 6);
+    return a.one;
+}
+
+// REDC(<M_row, z>) of one matrix row
+__device__ __forceinline__ Fp row_dot(const Args& a, int m, uint64_t k0, uint64_t k1, uint64_t i) {
+    Acc x;
+#pragma unroll
+    for (int j = 0; j < 14; j++) x.l[j] = 0;
+    const uint2* ent = a.e.ent[m];
+#pragma unroll 1
+    for (uint64_t k = k0; k < k1; k++) {
+        const uint2 e = ent[k];
+        const Fp z = load_z(a, i, e.x);
+        const uint32_t cls = e.y >> PAYLOAD_BITS, v = e.y & PAYLOAD;
+        if (cls == CLS_GEN) {
+            acc_add(x, fp_mul(z, a.e.table[v]));
+        } else {
+            const Fp s = cls == CLS_NEG ? neg_raw(z) : z;
+            if (v == 1)
+                acc_add(x, s);
+            else
+                acc_add_small(x, s, v);
+        }
+    }
+    return redc14(x);
+}
+
+template <bool EVAL>
+__global__ __launch_bounds__(64 * WAVES) void k_r1cs(Args a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t b = blockIdx.x * WAVES + wave;
+    const uint64_t i = (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);
+    if (b >= a.n_blk || i >= a.n) return;
+    const uint32_t blk = a.blk_first + b;
+    uint64_t r0 = a.e.blk[blk], r1 = a.e.blk[blk + 1];
+    r0 = r0 > a.row_lo ? r0 : a.row_lo;
+    r1 = r1 < a.row_hi ? r1 : a.row_hi;
+    uint64_t bad = ~0ull;
+#pragma unroll 1
+    for (uint64_t row = r0; row < r1; row++) {
+        const uint64_t a0 = a.e.rp[0][row], a1 = a.e.rp[0][row + 1], b0 = a.e.rp[1][row], b1 = a.e.rp[1][row + 1];
+        const uint64_t c0 = a.e.rp[2][row], c1 = a.e.rp[2][row + 1];
+        const Fp fa = a0 < a1 ? row_dot(a, 0, a0, a1, i) : fp_zero();
+        const Fp fb = b0 < b1 ? row_dot(a, 1, b0, b1, i) : fp_zero();
+        const Fp fc = c0 < c1 ? row_dot(a, 2, c0, c1, i) : fp_zero();
+        if (EVAL) {  // REDC(X) K = the row value in the input's form
+            const uint64_t o = (i * (a.row_hi - a.row_lo) + (row - a.row_lo)) * 6;
+            const Fp v[3] = {fp_mul(fa, a.k), fp_mul(fb, a.k), fp_mul(fc, a.k)};
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                uint4* dst = reinterpret_cast<uint4*>(a.out[m] + o);
+                dst[0] = make_uint4(v[m].l[0], v[m].l[1], v[m].l[2], v[m].l[3]);
+                dst[1] = make_uint4(v[m].l[4], v[m].l[5], v[m].l[6], v[m].l[7]);
+                dst[2] = make_uint4(v[m].l[8], v[m].l[9], v[m].l[10], v[m].l[11]);
+            }
+        } else {
+            const Fp lhs = (a0 < a1 && b0 < b1) ? fp_mul(fp_mul(fa, fb), a.k) : fp_zero();
+            if (!fp_eq(lhs, fc) && bad == ~0ull) bad = row;
+        }
+    }
+    if (!EVAL && bad != ~0ull) atomicMin(reinterpret_cast<unsigned long long*>(a.bad + i), (unsigned long long)bad);
+}
+
+// first index k of z with z_k >= p: grid (chunks, instances of this slice); a thread's indices ascend, so its first hit is its minimum
+__global__ __launch_bounds__(256) void k_r1cs_unreduced(const uint64_t* __restrict__ inst, uint64_t inst_stride, const uint64_t* __restrict__ wit,
+                                                        uint64_t wit_stride, uint32_t n_inst, uint64_t n_z, unsigned long long* __restrict__ out) {
+    constexpr uint32_t P[12] = BLSW_P_LIMBS;
+    const uint64_t i = blockIdx.y;
+#pragma unroll 1
+    for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n_z; k += (uint64_t)gridDim.x * 256) {
+        const uint64_t* src = k >= n_inst ? wit + (i * wit_stride + (k - n_inst)) * 6 : (inst ? inst + (i * inst_stride + k) * 6 : nullptr);
+        if (!src) continue;  // the constant one
+        const Fp z = load_fp(src);
+        uint32_t borrow = 0;
+#pragma unroll
+        for (int j = 0; j < 12; j++) subb32(z.l[j], P[j], borrow);
+        if (!borrow) {
+            atomicMin(out + i, (unsigned long long)k);
+            break;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------- host side
+int hip_ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) {
+        fprintf(stderr, "[blsw] r1cs %s: %s\n", what, hipGetErrorString(e));
+        return BLSW_ERR_HIP;
+    }
+    return BLSW_OK;
+}
+
+struct Key {
+    uint64_t w[6];
+    bool operator==(const Key& o) const { return memcmp(w, o.w, sizeof(w)) == 0; }
+};
+struct KeyHash {
+    size_t operator()(const Key& k) const {
+        uint64_t h = 0x9E3779B97F4A7C15ull;
+        for (int i = 0; i < 6; i++) h = (h ^ k.w[i]) * 0xBF58476D1CE4E5B9ull;
+        return (size_t)(h ^ (h >> 31));
+    }
+};
+
+// value < p and != 0 (6 little-endian u64 limbs)
+bool coefficient_ok(const uint64_t* v) {
+    static const uint64_t P64[6] = {0xb9feffffffffaaabull, 0x1eabfffeb153ffffull, 0x6730d2a0f6b0f624ull, 0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull,
+                                    0x1a0111ea397fe69aull};
+    if ((v[0] | v[1] | v[2] | v[3] | v[4] | v[5]) == 0) return false;
+    for (int i = 5; i >= 0; i--)
+        if (v[i] != P64[i]) return v[i] < P64[i];
+    return false;  // == p
+}
+
+struct Encoded {
+    std::vector<uint2> ent[3];
+    std::vector<Fp> table;
+    std::vector<uint64_t> blk;
+    uint64_t bytes = 0, off_rp[3] = {}, off_ent[3] = {}, off_table = 0, off_blk = 0;
+};
+
+uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
+
+// validates the CSR (include/blsw.h: blsw_r1cs_create) and encodes it; BLSW_ERR_ARG on the first rule it breaks
+int encode(const blsw_matrices_info_t* info, const blsw_matrices_t* m, Encoded* out) {
+    if (!info || !m || info->n_constraints == 0 || info->n_instance_vars == 0) return BLSW_ERR_ARG;
+    const uint64_t n_cons = info->n_constraints, n_z = info->n_instance_vars + info->n_witness;
+    if (n_z > 0xFFFFFFFFull) return BLSW_ERR_ARG;  // u32 columns
+    std::unordered_map<Key, uint32_t, KeyHash> codes;
+    std::vector<uint64_t> row_work(n_cons, W_ROW);
+    for (int mi = 0; mi < 3; mi++) {
+        const uint64_t* rp = m->row_ptr[mi];
+        const uint32_t* col = m->col[mi];
+        const uint64_t* val = m->val[mi];
+        const uint64_t nnz = info->nnz[mi];
+        if (!rp || (nnz && (!col || !val)) || rp[0] != 0 || rp[n_cons] != nnz) return BLSW_ERR_ARG;
+        std::vector<uint2>& ent = out->ent[mi];
+        ent.resize(nnz);
+        for (uint64_t r = 0; r < n_cons; r++) {
+            if (rp[r + 1] < rp[r] || rp[r + 1] > nnz) return BLSW_ERR_ARG;
+            for (uint64_t k = rp[r]; k < rp[r + 1]; k++) {
+                if (col[k] >= n_z || (k > rp[r] && col[k] <= col[k - 1])) return BLSW_ERR_ARG;
+                const uint64_t* v = val + k * 6;
+                if (!coefficient_ok(v)) return BLSW_ERR_ARG;
+                Key key;
+                memcpy(key.w, v, sizeof(key.w));
+                auto it = codes.find(key);
+                uint32_t code;
+                if (it != codes.end()) {
+                    code = it->second;
+                } else {  // canonical value c = v R^-1: +-c small, or a table entry
+                    Fp mont, one = fp_zero();
+                    memcpy(mont.l, v, sizeof(mont.l));
+                    one.l[0] = 1;
+                    const Fp c = fp_mul(mont, one), nc = fp_neg(c);
+                    auto small = [](const Fp& x) {
+                        uint32_t hi = 0;
+                        for (int j = 1; j < 12; j++) hi |= x.l[j];
+                        return hi == 0 && x.l[0] <= PAYLOAD;
+                    };
+                    if (small(c)) {
+                        code = CLS_POS << PAYLOAD_BITS | c.l[0];
+                    } else if (small(nc)) {
+                        code = CLS_NEG << PAYLOAD_BITS | nc.l[0];
+                    } else {
+                        if (out->table.size() > PAYLOAD) return BLSW_ERR_ARG;
+                        code = CLS_GEN << PAYLOAD_BITS | (uint32_t)out->table.size();
+                        out->table.push_back(mont);
+                    }
+                    codes.emplace(key, code);
+                }
+                ent[k] = make_uint2(col[k], code);
+                const uint32_t cls = code >> PAYLOAD_BITS, pv = code & PAYLOAD;
+                row_work[r] += cls == CLS_GEN ? W_GEN : (pv == 1 ? W_ONE : W_SMALL);
+            }
+        }
+    }
+    // blocks of about W_BLOCK work units (a row longer than that is a block of its own)
+    out->blk.assign(1, 0);
+    uint64_t acc = 0;
+    for (uint64_t r = 0; r < n_cons; r++) {
+        if (acc && acc + row_work[r] > W_BLOCK) {
+            out->blk.push_back(r);
+            acc = 0;
+        }
+        acc += row_work[r];
+    }
+    out->blk.push_back(n_cons);
+    if (out->blk.size() - 1 > 0xFFFFFFFFull / WAVES) return BLSW_ERR_ARG;
+    uint64_t off = 0;
+    for (int mi = 0; mi < 3; mi++) {
+        out->off_rp[mi] = off;
+        off = align256(off + (n_cons + 1) * 8);
+    }
+    for (int mi = 0; mi < 3; mi++) {
+        out->off_ent[mi] = off;
+        off = align256(off + info->nnz[mi] * 8);
+    }
+    out->off_table = off;
+    off = align256(off + out->table.size() * sizeof(Fp));
+    out->off_blk = off;
+    out->bytes = align256(off + out->blk.size() * 8);
+    return BLSW_OK;
+}
+
+}  // namespace
+
+struct blsw_r1cs {
+    int device;
+    uint64_t n_cons, n_inst, n_wit;
+    Enc enc;
+    std::vector<uint64_t> blk;  // host copy of the block starts (evaluate's row range -> blocks)
+};
+
+int blsw_r1cs_device_bytes(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t* bytes) {
+    if (!bytes) return BLSW_ERR_ARG;
+    Encoded e;
+    const int rc = encode(info, m, &e);
+    if (rc) return rc;
+    *bytes = e.bytes;
+    return BLSW_OK;
+}
+
+int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const blsw_matrices_t* m, int32_t device, void* d_buffer, uint64_t buffer_bytes,
+                     void* stream) {
+    if (!out || !d_buffer || (reinterpret_cast<uintptr_t>(d_buffer) & 255)) return BLSW_ERR_ARG;
+    *out = nullptr;
+    Encoded e;
+    int rc = encode(info, m, &e);
+    if (rc) return rc;
+    if (buffer_bytes < e.bytes) return BLSW_ERR_WORKSPACE;
+    int prev = -1, dev = device;
+    if (hip_ok(hipGetDevice(&prev), "hipGetDevice")) return BLSW_ERR_NO_DEVICE;
+    if (dev < 0) dev = prev;
+    if (dev != prev && hip_ok(hipSetDevice(dev), "hipSetDevice")) return BLSW_ERR_NO_DEVICE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(d_buffer);
+    auto put = [&](uint64_t off, const void* src, uint64_t bytes) {
+        return bytes ? hip_ok(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync") : BLSW_OK;
+    };
+    for (int mi = 0; mi < 3 && !rc; mi++) rc = put(e.off_rp[mi], m->row_ptr[mi], (info->n_constraints + 1) * 8);
+    for (int mi = 0; mi < 3 && !rc; mi++) rc = put(e.off_ent[mi], e.ent[mi].data(), e.ent[mi].size() * sizeof(uint2));
+    if (!rc) rc = put(e.off_table, e.table.data(), e.table.size() * sizeof(Fp));
+    if (!rc) rc = put(e.off_blk, e.blk.data(), e.blk.size() * 8);
+    if (!rc) rc = hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");  // the host vectors go out of scope
+    if (dev != prev) hipSetDevice(prev);
+    if (rc) return rc;
+    blsw_r1cs* r = new blsw_r1cs;
+    r->device = dev;
+    r->n_cons = info->n_constraints;
+    r->n_inst = info->n_instance_vars;
+    r->n_wit = info->n_witness;
+    for (int mi = 0; mi < 3; mi++) {
+        r->enc.rp[mi] = reinterpret_cast<const uint64_t*>(base + e.off_rp[mi]);
+        r->enc.ent[mi] = reinterpret_cast<const uint2*>(base + e.off_ent[mi]);
+    }
+    r->enc.table = reinterpret_cast<const Fp*>(base + e.off_table);
+    r->enc.blk = reinterpret_cast<const uint64_t*>(base + e.off_blk);
+    r->blk = std::move(e.blk);
+    *out = r;
+    return BLSW_OK;
+}
+
+int blsw_r1cs_destroy(blsw_r1cs_t* r) {
+    delete r;
+    return BLSW_OK;
+}
+
+namespace {
+
+// the argument rules shared by check and evaluate (host only)
+int io_args(const blsw_r1cs* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n, uint32_t form) {
+    if (!r || !d_witness || n == 0 || form > 1 || witness_stride < r->n_wit) return BLSW_ERR_ARG;
+    if (r->n_inst > 1 && (!d_instance || instance_stride < r->n_inst)) return BLSW_ERR_ARG;
+    if (d_instance && instance_stride < r->n_inst) return BLSW_ERR_ARG;
+    return BLSW_OK;
+}
+
+Args make_args(const blsw_r1cs* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n, uint32_t form) {
+    Args a;
+    memset(&a, 0, sizeof(a));
+    a.e = r->enc;
+    a.inst = d_instance;
+    a.wit = d_witness;
+    a.inst_stride = instance_stride;
+    a.wit_stride = witness_stride;
+    a.n = n;
+    a.n_inst = (uint32_t)r->n_inst;
+    a.one = form ? fp_zero() : fp_one();
+    if (form) a.one.l[0] = 1;
+    return a;
+}
+
+Fp fp_const(const uint32_t (&l)[12]) {
+    Fp r;
+    memcpy(r.l, l, sizeof(r.l));
+    return r;
+}
+
+// grid.y <= 65535 groups of 64 instances per launch
+int launch(Args a, bool eval, hipStream_t st) {
+    const uint64_t n = a.n;
+    const Args base = a;
+    for (uint64_t first = 0; first < n; first += 65535ull * 64) {
+        a = base;
+        const uint64_t cnt = n - first < 65535ull * 64 ? n - first : 65535ull * 64;
+        a.n = cnt;
+        a.wit = base.wit + first * base.wit_stride * 6;
+        if (base.inst) a.inst = base.inst + first * base.inst_stride * 6;
+        if (base.bad) a.bad = base.bad + first;
+        for (int m = 0; m < 3; m++)
+            if (base.out[m]) a.out[m] = base.out[m] + first * (base.row_hi - base.row_lo) * 6;
+        dim3 grid((a.n_blk + WAVES - 1) / WAVES, (unsigned)((cnt + 63) / 64));
+        if (eval)
+            hipLaunchKernelGGL(k_r1cs<true>, grid, dim3(64 * WAVES), 0, st, a);
+        else
+            hipLaunchKernelGGL(k_r1cs<false>, grid, dim3(64 * WAVES), 0, st, a);
+    }
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+struct Guard {
+    int prev = -1;
+    bool switched = false;
+    explicit Guard(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+    }
+    ~Guard() {
+        if (switched) hipSetDevice(prev);
+    }
+};
+
+}  // namespace
+
+int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
+                    uint32_t form, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (io_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form) || !d_first_unsatisfied) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
+    static constexpr uint32_t R2[12] = BLSW_R2_LIMBS, R3[12] = BLSW_R3_LIMBS;
+    a.k = fp_const(form ? R3 : R2);
+    a.blk_first = 0;
+    a.n_blk = (uint32_t)(r->blk.size() - 1);
+    a.row_lo = 0;
+    a.row_hi = r->n_cons;
+    a.bad = reinterpret_cast<uint64_t*>(d_first_unsatisfied);
+    if (hip_ok(hipMemsetAsync(d_first_unsatisfied, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;  // all ones = -1 = satisfied
+    int rc = launch(a, false, st);
+    if (rc || !d_first_unreduced) return rc;
+    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
+    const uint64_t n_z = r->n_inst + r->n_wit, chunks = (n_z + 255) / 256;
+    for (uint64_t first = 0; first < n; first += 65535) {
+        const uint64_t cnt = n - first < 65535 ? n - first : 65535;
+        dim3 grid((unsigned)(chunks < 64 ? chunks : 64), (unsigned)cnt);
+        hipLaunchKernelGGL(k_r1cs_unreduced, grid, dim3(256), 0, st, d_instance ? d_instance + first * instance_stride * 6 : nullptr, instance_stride,
+                           d_witness + first * witness_stride * 6, witness_stride, (uint32_t)r->n_inst, n_z,
+                           reinterpret_cast<unsigned long long*>(d_first_unreduced + first));
+    }
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+int blsw_r1cs_evaluate(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
+                       uint32_t form, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream) {
+    if (io_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form) || !d_az || !d_bz || !d_cz) return BLSW_ERR_ARG;
+    if (row_count == 0 || row_begin >= r->n_cons || row_count > r->n_cons - row_begin) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
+    static constexpr uint32_t R2[12] = BLSW_R2_LIMBS;
+    a.k = fp_const(R2);
+    a.row_lo = row_begin;
+    a.row_hi = row_begin + row_count;
+    // blocks [b0, b1) that hold rows of the range
+    const auto& blk = r->blk;
+    const uint64_t b0 = (uint64_t)(std::upper_bound(blk.begin(), blk.end(), a.row_lo) - blk.begin()) - 1;
+    const uint64_t b1 = (uint64_t)(std::lower_bound(blk.begin(), blk.end(), a.row_hi) - blk.begin());
+    a.blk_first = (uint32_t)b0;
+    a.n_blk = (uint32_t)(b1 - b0);
+    a.out[0] = d_az;
+    a.out[1] = d_bz;
+    a.out[2] = d_cz;
+    return launch(a, true, st);
+}

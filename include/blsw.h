@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 10
+#define BLSW_ABI_VERSION 11
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -327,6 +327,36 @@ int blsw_matrices_fill_params(uint32_t msg_len, uint32_t params_mode, const blsw
  * blsw_layout_t.pk_mode (ark-relations' ConstraintMatrices: instance variables first, then the witnesses) */
 int blsw_matrices_info_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, blsw_matrices_info_t* out);
 int blsw_matrices_fill_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out);
+
+/* Device R1CS evaluator (ABI 11): checks and evaluates the matrices above against witness vectors on the GPU — arkworks'
+ * cs.is_satisfied() / cs.which_is_unsatisfied() and the A z, B z, C z a prover computes first, for n instances at a time.
+ * A handle is built once per circuit shape from the host CSR blsw_matrices_fill* wrote: create validates and encodes it (every entry a u32
+ * column and a u32 code: +-v for |coefficient| < 2^30, else an index into a table of the distinct Montgomery coefficients; rows cut into
+ * blocks of about equal work) into the caller's device buffer (256-byte aligned) of blsw_r1cs_device_bytes bytes, which must outlive the handle.
+ * Element form and strides:
+ *   z = [instance | witness], columns numbered as in blsw_matrices_info_io (0 = the constant one, then the public inputs, then witness k at
+ *   n_instance_vars + k). d_witness [n][witness_stride] and d_instance [n][instance_stride] elements of 6 u64 (strides in field elements,
+ *   witness_stride >= n_witness, instance_stride >= n_instance_vars) — the layout blsw_engine_submit / blsw_engine_submit_io write.
+ *   form: 0 = Montgomery (the engine's default), 1 = canonical integers (options.output_form 1); every input element in that form.
+ *   n_instance_vars == 1: d_instance may be NULL, the constant one is then R mod p (form 0) or 1 (form 1). n_instance_vars > 1: required.
+ *   The check assumes reduced elements (< p); blsw_r1cs_check reports the first unreduced one on request.
+ * Every argument rule is checked on the host before any HIP call: BLSW_ERR_ARG for a row_ptr that does not start at 0, decreases or
+ * does not end at nnz, columns not strictly ascending within a row or not below n_instance_vars + n_witness, a zero coefficient or one
+ * >= p, form > 1, n == 0, a stride below the element count, a missing instance vector, a row range outside the matrix.
+ * Calls are asynchronous on `stream` (hipStream_t) and run on the handle's device; results leave through vector stores and global atomics. */
+typedef struct blsw_r1cs blsw_r1cs_t;
+int blsw_r1cs_device_bytes(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t* bytes);
+/* device: HIP ordinal, -1 = the current device. The encoding is copied on `stream`; create synchronises it before it returns. */
+int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const blsw_matrices_t* m, int32_t device, void* d_buffer, uint64_t buffer_bytes,
+                     void* stream);
+int blsw_r1cs_destroy(blsw_r1cs_t* r);
+/* d_first_unsatisfied [n] int64: index of the first constraint j with <A_j, z> * <B_j, z> != <C_j, z>, or -1 when z satisfies the system.
+ * d_first_unreduced [n] int64 (may be NULL): the first index k of z with z_k >= p, or -1. */
+int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
+                    uint32_t form, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+/* rows [row_begin, row_begin + row_count): d_az / d_bz / d_cz [n][row_count][6] u64 = <A_j, z>, <B_j, z>, <C_j, z> reduced, in the input's form */
+int blsw_r1cs_evaluate(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
+                       uint32_t form, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
 
 /* Input decode (PublicKey::try_from / Signature::try_from -> deserialize_compressed, src/bls.rs:219-242, 316-339):
  *   d_pk48 [n][48], d_sig96 [n][96]  ZCash-format compressed points

@@ -124,6 +124,7 @@ class ConstraintSystem {
         check(blsw_layout(msg_len, &layout_), "blsw_layout");
     }
     ~ConstraintSystem() {
+        if (r1cs_) blsw_r1cs_destroy(r1cs_);
         if (engine_) blsw_engine_destroy(engine_);
     }
     ConstraintSystem(const ConstraintSystem&) = delete;
@@ -136,13 +137,26 @@ class ConstraintSystem {
     uint64_t num_witness_variables() const { return layout_.n_witness; }
     uint64_t num_instance_variables() const { return layout_.n_instance_vars; }
     // cs.num_constraints(): the library synthesises the system symbolically on the host (a few seconds, once per call)
-    uint64_t num_constraints() const {
-        blsw_matrices_info_t info;
-        check(layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
-              : layout_.params_mode              ? blsw_matrices_info_params(msg_len_, layout_.params_mode, &info)
-                                                 : blsw_matrices_info(msg_len_, layout_.n_keys, 1, &info),
-              "blsw_matrices_info");
-        return info.n_constraints;
+    uint64_t num_constraints() const { return matrices_info().n_constraints; }
+    // cs.which_is_unsatisfied() of every one of the n systems after verify, on the device (blsw_r1cs_check over the witness and instance vectors
+    // this object holds): the index of the first unsatisfied constraint, or -1. The first call synthesises the matrices on the host and encodes
+    // them on the device (a few seconds, once per object).
+    std::vector<int64_t> which_is_unsatisfied() {
+        if (!witness_.get()) throw Error("which_is_unsatisfied before verify", BLSW_ERR_ARG);
+        if (!r1cs_) build_checker();
+        detail::DeviceBytes d_bad(n_ * 8);
+        const bool io = layout_.n_instance_vars > 1;
+        check(blsw_r1cs_check(r1cs_, io ? static_cast<const uint64_t*>(instance_.get()) : nullptr, layout_.n_instance_vars, static_cast<const uint64_t*>(witness_.get()),
+                              layout_.n_witness, n_, 0, static_cast<int64_t*>(d_bad.get()), nullptr, nullptr),
+              "blsw_r1cs_check");
+        std::vector<int64_t> bad(n_);
+        d_bad.download(bad.data(), n_ * 8);
+        return bad;
+    }
+    // cs.is_satisfied() of system i (one check of all n systems per call: call which_is_unsatisfied() once for a whole batch)
+    bool is_satisfied(size_t i) {
+        if (i >= n_) throw Error("is_satisfied out of range", BLSW_ERR_ARG);
+        return which_is_unsatisfied()[i] < 0;
     }
     const blsw_layout_t& layout() const { return layout_; }
     // witness_assignment of system i after verify: n_witness elements of 6 little-endian u64 limbs (Montgomery form: arkworks' in-memory Fq)
@@ -180,6 +194,38 @@ class ConstraintSystem {
     blsw_layout_t layout_;
     blsw_engine_t* engine_ = nullptr;
     detail::DeviceBytes workspace_, witness_, instance_, result_, d_status_, pk_xy_, sig_xy_;
+    blsw_r1cs_t* r1cs_ = nullptr;  // the device checker (which_is_unsatisfied), built at its first use
+    detail::DeviceBytes r1cs_buffer_;
+    blsw_matrices_info_t matrices_info() const {
+        blsw_matrices_info_t info;
+        check(layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
+              : layout_.params_mode              ? blsw_matrices_info_params(msg_len_, layout_.params_mode, &info)
+                                                 : blsw_matrices_info(msg_len_, layout_.n_keys, 1, &info),
+              "blsw_matrices_info");
+        return info;
+    }
+    void build_checker() {
+        blsw_matrices_info_t info = matrices_info();
+        std::vector<uint64_t> rp[3], val[3];
+        std::vector<uint32_t> col[3];
+        blsw_matrices_t m;
+        for (int k = 0; k < 3; k++) {
+            rp[k].resize(info.n_constraints + 1);
+            col[k].resize(info.nnz[k]);
+            val[k].resize(info.nnz[k] * 6);
+            m.row_ptr[k] = rp[k].data();
+            m.col[k] = col[k].data();
+            m.val[k] = val[k].data();
+        }
+        check(layout_.pk_mode || layout_.sig_mode ? blsw_matrices_fill_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info, &m)
+              : layout_.params_mode              ? blsw_matrices_fill_params(msg_len_, layout_.params_mode, &info, &m)
+                                                 : blsw_matrices_fill(msg_len_, layout_.n_keys, 1, &info, &m),
+              "blsw_matrices_fill");
+        uint64_t bytes = 0;
+        check(blsw_r1cs_device_bytes(&info, &m, &bytes), "blsw_r1cs_device_bytes");
+        r1cs_buffer_ = detail::DeviceBytes(bytes);
+        check(blsw_r1cs_create(&r1cs_, &info, &m, device_, r1cs_buffer_.get(), bytes, nullptr), "blsw_r1cs_create");
+    }
     // AllocationMode of the key / the signature: part of the circuit shape (blsw_layout_io)
     void set_io(uint32_t pk_mode, uint32_t sig_mode) {
         if (engine_) throw Error("new_variable after verify", BLSW_ERR_ARG);

@@ -16,9 +16,10 @@ HEADER = os.path.join(ROOT, "include", "blsw.h")
 INTEGRATION = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED RUST BINDING (tools/gen_bindings.py) -->", "<!-- END GENERATED RUST BINDING -->"
 
-SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int": "i32", "float": "f32", "double": "f64", "void": "c_void"}
+SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64", "int": "i32", "float": "f32", "double": "f64", "void": "c_void"}
 STRUCT_NAMES = {"blsw_layout_t": "BlswLayout", "blsw_engine_options_t": "BlswEngineOptions", "blsw_engine_t": "BlswEngine",
-                "blsw_matrices_t": "BlswMatrices", "blsw_matrices_info_t": "BlswMatricesInfo"}
+                "blsw_matrices_t": "BlswMatrices", "blsw_matrices_info_t": "BlswMatricesInfo",
+                "blsw_r1cs_t": "BlswR1cs"}
 
 
 def strip_comments(text):

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Rate of the device R1CS evaluator (blsw_r1cs_check / _evaluate) on the single-key shape, one JSON line:
+    check_instances_per_s, check_ms_per_1024   the satisfaction check of a batch of n (default 1 024) engine-written witness vectors
+    unreduced_ms_per_1024                       the separate first-unreduced pass (HBM stream of the vectors)
+    evaluate_instances_per_s                    A z, B z, C z of every row for a slice of the batch (output n x 3 x 34 MB)
+    products_per_instance                       product-equivalents counted from the encoded class histogram (a table coefficient = 1,
+                                                a row = 3 reductions of half a product + 2 products), and the rate that implies
+
+    python tools/r1cs_rate.py [--n 1024] [--reps 3] [--eval-n 64]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+P_MOD = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+
+
+def class_histogram(mats):
+    """entries per class as blsw_r1cs_create encodes them: +-1, other |c| < 2^30, table (everything else); rows with non-empty A and B"""
+    r_inv = pow(1 << 384, -1, P_MOD)
+    h = {"one": 0, "small": 0, "table": 0}
+    for name in "ABC":
+        _, _, val = mats[name]
+        uniq, counts = np.unique(val, axis=0, return_counts=True)
+        for v, c in zip(uniq, counts):
+            x = sum(int(w) << (64 * k) for k, w in enumerate(v)) * r_inv % P_MOD
+            s = min(x, P_MOD - x)
+            h["one" if s == 1 else ("small" if s < (1 << 30) else "table")] += int(c)
+    ra, rb = (np.diff(mats[k][0].astype(np.int64)) > 0 for k in "AB")
+    h["rows"] = int(mats["n_constraints"])
+    h["rows_ab"] = int((ra & rb).sum())
+    return h
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--eval-n", type=int, default=64)
+    a = ap.parse_args()
+    import torch
+
+    pkg = importlib.import_module("bls-verify-gadget_amd")
+    workload = importlib.import_module("bls-verify-gadget_amd.workload")
+    dev = torch.device("cuda:0")
+    t0 = time.time()
+    mats = pkg.matrices(32)
+    t_mats = time.time() - t0
+    t0 = time.time()
+    chk = pkg.ConstraintChecker.from_matrices(mats, dev)
+    t_create = time.time() - t0
+    pk, msg, sig, _ = workload.make_batch(pkg, a.n, device=dev)
+    eng = pkg.WitnessEngine(a.n, 32, max_steps=16, device=dev, n_buffers=3)
+    w = eng.new_witness_tensor()
+    eng.submit(pk, sig, msg, witness=w)
+    eng.flush()
+    torch.cuda.synchronize()
+    eng.close()
+
+    def timed(fn):
+        fn()  # warm-up
+        torch.cuda.synchronize()
+        best = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            best.append(e0.elapsed_time(e1))
+        return min(best), out
+
+    ms_check, bad = timed(lambda: chk.which_is_unsatisfied(w))
+    ms_both, _ = timed(lambda: chk.first_unreduced(w))
+    ok = int((bad < 0).sum().item())
+    we = w[:a.eval_n]
+    ms_eval, _ = timed(lambda: chk.evaluate(we))
+    h = class_histogram(mats)
+    prod = h["table"] + 1.5 * h["rows"] + 2 * h["rows_ab"]
+    print(json.dumps({
+        "metric": "r1cs_check_single_key", "n": a.n, "satisfied": ok,
+        "check_instances_per_s": round(a.n / (ms_check / 1e3), 1), "check_ms_per_1024": round(ms_check * 1024 / a.n, 3),
+        "unreduced_ms_per_1024": round((ms_both - ms_check) * 1024 / a.n, 3),
+        "evaluate_instances_per_s": round(a.eval_n / (ms_eval / 1e3), 1), "eval_n": a.eval_n,
+        "products_per_instance": int(prod), "implied_products_per_s": round(prod * a.n / (ms_check / 1e3) / 1e9, 2) * 1e9,
+        "classes": h, "device_bytes": chk.buffer.numel(), "host_matrices_s": round(t_mats, 2), "create_s": round(t_create, 2),
+    }))
+
+
+if __name__ == "__main__":
+    main()
