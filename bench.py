@@ -18,6 +18,12 @@ the north-star's all-gather of witness shards is timed separately (`value_with_a
 every step leaves the engine in its compact wire form (bit-packed SHA witnesses + field witnesses, 2.6 MB per instance), THAT is
 all-gathered over RCCL, and every rank expands all ranks' batches back into full witness tensors (34 MB per instance), each
 consumed by the digest kernel before the next; `--allgather-form full` gathers the full tensors in micro-batches instead.
+
+A plain run does only what the headline needs: it mints the inputs, warms up, times the K steps, writes `--dump-outputs` and
+prints the line (the `roofline` of k_sha_expand comes from HIP events of the timed launches, `results_ok` from the timed steps'
+results). `--full` adds everything that takes work of its own: the same-box fill yardstick, the VALU rooflines (micro-benchmarks),
+`witness_ok` (a direct-mode engine re-runs the batch), the gathered result shards, the consumer-mode, all-gather and side legs, and
+the CPU baseline.
 """
 import argparse
 import importlib
@@ -58,6 +64,9 @@ def parse_args():
     ap.add_argument("--outputs", type=int, default=2, help="ring of output witness tensors (34 MB x batch each)")
     ap.add_argument("--mem-frac", type=float, default=0.68, help="share of the free HBM the engine workspace and the output ring may take")
     ap.add_argument("--expand-variant", type=int, default=-1, help="options.expand_variant of the timed engine (-1 = the library's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the yardsticks, rooflines, checks and legs that take work of their own (see the module docstring); --no-cpu-baseline, "
+                         "--cpu-sample, --consumer-*, --allgather-* and --side-legs shape what it adds")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=256, help="instances of the batch timed on the host (all cores, and one thread)")
     ap.add_argument("--consumer-shard", type=int, default=8192,
@@ -594,7 +603,7 @@ def main():
 
     # same-box yardstick: what this box's memory system gives a plain fill of one witness tensor in the expansion's store geometry (boxes of the pool
     # differ by 20-30 %; the tensor is overwritten by the warm-up steps)
-    fill_bps = pkg.fill_rate(outs[0], reps=2)
+    fill_bps = pkg.fill_rate(outs[0], reps=2) if args.full else None
     for k in range(args.warmup):
         step(k)
     eng.flush()
@@ -626,7 +635,7 @@ def main():
     ok = bool((res.cpu().numpy().astype(bool) == expect[None, :]).all())
     # what the timed region left in the ring: every step submitted the same batch, so each ring tensor must hold exactly the
     # witness vectors a direct-mode engine (chains write in place, no staging, no expansion ordering) produces for that batch
-    ring_digests = [pkg.witness_digest(o).cpu() for o in outs]
+    ring_digests = [pkg.witness_digest(o).cpu() for o in outs] if args.full else None
     gathered_ok = None
     per_rank_dt = [dt]
     if dist:
@@ -636,22 +645,25 @@ def main():
         per_rank_dt = [float(x.item()) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        allres = sharding.all_gather_results(results[0], n * world)  # result shards only (multi-GPU)
-        gathered_ok = bool(allres.numel() == n * world)
+        if args.full:
+            allres = sharding.all_gather_results(results[0], n * world)  # result shards only (multi-GPU)
+            gathered_ok = bool(allres.numel() == n * world)
     eng.close()
     del eng
-    direct = pkg.WitnessEngine(n, 32, max_steps=1, device=dev, n_buffers=1)
-    direct.submit(d_pk, d_sig, d_msg, witness=outs[0], result=results[0])
-    direct.flush()
-    torch.cuda.synchronize()
-    ref_digest = pkg.witness_digest(outs[0]).cpu()
-    direct.close()
-    witness_ok = bool(all(torch.equal(d, ref_digest) for d in ring_digests)) and bool(ref_digest.abs().sum().item() != 0)
-    del direct, outs
-    torch.cuda.empty_cache()
+    witness_ok = None
+    if args.full:
+        direct = pkg.WitnessEngine(n, 32, max_steps=1, device=dev, n_buffers=1)
+        direct.submit(d_pk, d_sig, d_msg, witness=outs[0], result=results[0])
+        direct.flush()
+        torch.cuda.synchronize()
+        ref_digest = pkg.witness_digest(outs[0]).cpu()
+        direct.close()
+        witness_ok = bool(all(torch.equal(d, ref_digest) for d in ring_digests)) and bool(ref_digest.abs().sum().item() != 0)
+        del direct, outs
+        torch.cuda.empty_cache()
 
     consumer = None
-    if world == 1 and args.consumer_shard >= 2 * n:  # the real-use rate: a consumer reads every tensor before it is overwritten
+    if args.full and world == 1 and args.consumer_shard >= 2 * n:  # the real-use rate: a consumer reads every tensor before it is overwritten
         try:
             shard = args.consumer_shard // n * n
             stream_shard = importlib.import_module("tools.shard_rehearsal").stream_shard  # the measurement harness of the consumer legs (not product code)
@@ -694,7 +706,7 @@ def main():
         torch.cuda.empty_cache()
 
     ag = None
-    if dist and args.allgather_steps > 0:
+    if args.full and dist and args.allgather_steps > 0:
         leg = allgather_leg_compact if (args.allgather_form == "compact" and n % 64 == 0) else allgather_leg
         try:  # the second leg never takes the headline line down with it
             ag = leg(args, pkg, sharding, dist, dev, (d_pk, d_msg, d_sig), lay, world)
@@ -710,7 +722,6 @@ def main():
     expand_bytes = n * lay["sha_bits"] * 48  # bytes one k_sha_expand launch must write
     achieved = expand_bytes / (exp_avg_ms * 1e-3) / 1e9 if exp_avg_ms else 0.0
     bytes_per_instance = 48 * (lay["n_witness"] + lay["n_instance_vars"]) + 320
-    opc = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_opcount.json")))
     # HBM bytes per k_sha_expand launch from the PMC passes committed under profiles/ (rocprofv3 --pmc cannot be combined
     # with the timed run); only quoted for the workload it was collected on
     traffic, traffic_source, whole_step, whole_step_file = None, None, None, None
@@ -726,10 +737,6 @@ def main():
                 break
         except (OSError, KeyError, ValueError):
             continue
-    mad_per_instance = (opc["fp_mul"] + opc["fp_inv"] * FPMUL_PER_INV) * MAD_PER_FPMUL
-    executed_fpmul = opc["fp_mul"] + opc["fp_inv"] * FPMUL_PER_INV_EXECUTED
-    mad_peak = pkg.microbench(0, iters=8192, blocks=8192)
-    fpmul_peak = pkg.microbench(1, iters=512, blocks=8192)
     out = {
         "metric": "BLS-verify witness instances/sec (full pairing circuit)",
         "value": value,
@@ -753,18 +760,24 @@ def main():
         "roofline": {"bound": "hbm", "kernel": "k_sha_expand", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                      "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes_per_launch": expand_bytes, "avg_launch_ms": exp_avg_ms, "launches_timed": exp_count,
                      # the same-box yardstick: a plain fill of one witness tensor in the kernel's store geometry, measured before the timed region
-                     "fill_GBps": fill_bps / 1e9, "frac_of_fill": achieved / (fill_bps / 1e9) if fill_bps else None},
+                     "fill_GBps": fill_bps / 1e9 if fill_bps else None, "frac_of_fill": achieved / (fill_bps / 1e9) if fill_bps else None},
         "roofline_whole_path": {"bound": "hbm", "algorithmic_bytes_per_instance": bytes_per_instance,
                                 "achieved": value / world * bytes_per_instance / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                 "frac": value / world * bytes_per_instance / 1e9 / HBM_PEAK_GBPS},
-        "roofline_valu": {"bound": "valu-int32-mad", "algorithmic_mad_per_instance": mad_per_instance, "measured_peak_mad_per_s": mad_peak,
-                          "measured_peak_fpmul_per_s": fpmul_peak, "achieved_mad_per_s": value / world * mad_per_instance,
-                          "frac": value / world * mad_per_instance / mad_peak},
+    }
+    if args.full:
+        opc = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_opcount.json")))
+        mad_per_instance = (opc["fp_mul"] + opc["fp_inv"] * FPMUL_PER_INV) * MAD_PER_FPMUL
+        executed_fpmul = opc["fp_mul"] + opc["fp_inv"] * FPMUL_PER_INV_EXECUTED
+        mad_peak = pkg.microbench(0, iters=8192, blocks=8192)
+        fpmul_peak = pkg.microbench(1, iters=512, blocks=8192)
+        out["roofline_valu"] = {"bound": "valu-int32-mad", "algorithmic_mad_per_instance": mad_per_instance, "measured_peak_mad_per_s": mad_peak,
+                                "measured_peak_fpmul_per_s": fpmul_peak, "achieved_mad_per_s": value / world * mad_per_instance,
+                                "frac": value / world * mad_per_instance / mad_peak}
         # utilisation, not Fermat-priced throughput: Fp products the kernels actually execute per instance (products of the
         # op counter + 27 product-times per safegcd inversion) over the measured Fp-product rate of the chip
-        "roofline_valu_executed": {"bound": "valu-fp-mul", "executed_fpmul_per_instance": executed_fpmul, "achieved_fpmul_per_s": value / world * executed_fpmul,
-                                   "measured_peak_fpmul_per_s": fpmul_peak, "frac": value / world * executed_fpmul / fpmul_peak},
-    }
+        out["roofline_valu_executed"] = {"bound": "valu-fp-mul", "executed_fpmul_per_instance": executed_fpmul, "achieved_fpmul_per_s": value / world * executed_fpmul,
+                                         "measured_peak_fpmul_per_s": fpmul_peak, "frac": value / world * executed_fpmul / fpmul_peak}
     if whole_step and whole_step["instances_per_step"] == n and lay["msg_len"] == 32:
         # every byte the HBM moves per step (PMC, all kernels) over the measured step time: what the memory system delivers to
         # the path as a whole — the expansion's own figure above is lower because the other kernels' traffic runs beside it
@@ -783,9 +796,9 @@ def main():
         if ag_dt:
             out["value_with_allgather"] = n * world * ag_steps / ag_dt
         out["allgather"] = dict({"steps": ag_steps, "seconds": ag_dt}, **ag_info)
-    if world == 1 and args.side_legs:
+    if args.full and world == 1 and args.side_legs:
         out["side"] = side_legs(args, pkg, workload, dev, fpmul_peak, opc)
-    if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only: the other ranks of a multi-GPU run would wait ~15 s in the final barrier
+    if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only: the other ranks of a multi-GPU run would wait ~15 s in the final barrier
         out["cpu_baseline"] = cpu_baseline(args, d_pk, d_msg, d_sig, n)
     print(json.dumps(out))
 

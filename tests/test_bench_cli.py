@@ -1,9 +1,10 @@
 """bench.py host logic without a GPU: --gpus N outside a launcher starts N ranks as a CHILD torch.distributed.run (never an
 exec of a process that touched the GPU) and relays rank 0's JSON line; launch groups are balanced; the CPU share honours the
-cgroup quota."""
+cgroup quota. On the GPU: a plain run prints the headline line and writes --dump-outputs, and leaves everything else to --full."""
 import importlib.util
 import json
 import os
+import subprocess
 import sys
 
 import pytest
@@ -97,3 +98,44 @@ def test_dump_outputs_files_exact_and_seeded(bench, tmp_path, monkeypatch):
     assert len({tuple(r) for r in limbs.tolist()}) == n * nw  # the sample reaches every element of a small tensor
     bench.dump_outputs(Pkg, str(tmp_path / "c"), w, res, rank=1, world=2)
     assert np.load(tmp_path / "c" / "witness_sample_rank1.npy").shape[0] == sample.shape[0] // 2
+
+
+def test_full_is_off_by_default_and_reaches_the_ranks(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse_args().full is False
+    seen = {}
+
+    class P:
+        returncode = 0
+        stdout = json.dumps({"metric": "m"}) + "\n"
+
+    def fake_run(cmd, env=None, stdout=None, text=None):
+        seen["cmd"] = cmd
+        return P()
+
+    monkeypatch.setattr(bench.subprocess, "run", fake_run)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full"])
+    args = bench.parse_args()
+    assert args.full is True
+    with pytest.raises(SystemExit):
+        bench.spawn_ranks(args)
+    assert seen["cmd"][-3:] == ["--gpus", "2", "--full"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only(tmp_path):
+    """`bench.py` without --full: one JSON line with the headline fields and right results, the dumped arrays, and none of the
+    yardsticks, checks or legs that --full adds. Not a measurement."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "128",
+                        "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "instances/s" and out["higher_is_better"] is True and out["value"] > 0 and "dtype" in out
+    assert out["steps"] == 2 and out["warmup"] == 1 and abs(out["ms_per_step"] - 128 / out["value"] * 1e3) < 1e-6 * out["ms_per_step"]
+    assert out["config"]["results_ok"] is True and out["roofline"]["launches_timed"] > 0
+    assert out["witness_ok"] is None and out["roofline"]["fill_GBps"] is None
+    for key in ("side", "cpu_baseline", "consumer_mode", "value_consumer_mode", "allgather", "roofline_valu", "roofline_valu_executed"):
+        assert key not in out, key
+    assert sorted(os.listdir(tmp_path)) == ["result.npy", "witness_digest.npy", "witness_sample.npy"]
+    assert out["dump_outputs"]["arrays"]["result"] == [128]

@@ -54,12 +54,12 @@ def test_two_ranks_on_one_gpu_rehearsal():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_gloo_child():
-    """`python bench.py --gpus 2 --steps 4` as the driver would start it for N = 2 (bench.py spawns its own child torch.distributed.run),
+    """`python bench.py --gpus 2 --steps 4 --full` as the driver would start it for N = 2 (bench.py spawns its own child torch.distributed.run),
     with BLSW_TEST_BACKEND=gloo so that both ranks may share the one GPU of the builder's box: the line must carry the world size, the
     backend, per-rank rates, generation-only next to the all-gather leg, and right witnesses. Not a measurement."""
     env = dict(os.environ, BLSW_TEST_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "128", "--allgather-steps", "4",
-                        "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, p.stderr[-2000:]
     out = json.loads(lines[-1])

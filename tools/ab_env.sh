@@ -12,10 +12,10 @@ shift
 mkdir -p gpurun_out
 for rep in $(seq 1 $reps); do
 for e in "${envs[@]}"; do
-  env $e timeout -k 10 400 python bench.py --no-cpu-baseline --side-legs 0 "$@" > gpurun_out/ab_line.json 2> gpurun_out/ab_line.err || { tail -5 gpurun_out/ab_line.err; exit 1; }
-  python - "$e" "$*" >> $out <<'PY'
+  env $e timeout -k 10 400 python bench.py --full --no-cpu-baseline --side-legs 0 "$@" > $out.line.json 2> $out.line.err || { tail -5 $out.line.err; exit 1; }
+  python - "$e" "$*" $out.line.json >> $out <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/ab_line.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])
 r = d["roofline"]
 print("%-36s %-24s value %7d  ms/step %6.3f  k_sha_expand %6.3f ms (%4.2f of 8 TB/s, %4.2f of this box's fill)  consumer %6s steady %6s  witness_ok %s" % (
     sys.argv[1], sys.argv[2], round(d["value"]), d["ms_per_step"], r["avg_launch_ms"], r["frac"], r.get("frac_of_fill") or 0,

@@ -7,8 +7,8 @@ TAG=${1:-r05}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${TAG}prof
 mkdir -p $O
-cd $R && python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
-python3 bench.py --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err || exit 1
+cd $R && python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err || exit 1
 python3 tools/digest_rate.py > $O/digest_rate.json 2> $O/digest_rate.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --no-cpu-baseline --consumer-shard 0 --side-legs 0 > $O/stats_bench.json 2> $O/stats.err || exit 1
