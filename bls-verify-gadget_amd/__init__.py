@@ -29,7 +29,7 @@ class blsw_layout_t(ctypes.Structure):
 
 
 class blsw_engine_options_t(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode".split()]
+    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode msg_mode".split()]
 
 
 class blsw_matrices_info_t(ctypes.Structure):
@@ -96,6 +96,9 @@ def lib():
         L.blsw_matrices_info_params.argtypes = [u32, u32, ctypes.POINTER(blsw_matrices_info_t)]
         L.blsw_matrices_fill_params.argtypes = [u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
         L.blsw_layout_params.argtypes = [u32, u32, ctypes.POINTER(blsw_layout_t)]
+        L.blsw_layout_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_layout_t)]
+        L.blsw_matrices_info_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t)]
+        L.blsw_matrices_fill_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
         L.blsw_layout_multi.argtypes = [u32, u32, ctypes.POINTER(blsw_layout_t)]
         L.blsw_verify_multi_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
         L.blsw_verify_multi_batch.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, vp, u64, vp]
@@ -136,22 +139,29 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_decode_batch", "blsw_layout_aggregate", "blsw_aggregate_workspace_bytes", "blsw_aggregate_verify_batch", "blsw_layout_multi",
                     "blsw_verify_multi_workspace_bytes", "blsw_verify_multi_batch", "blsw_matrices_info", "blsw_matrices_fill", "blsw_sign_batch", "blsw_microbench", "blsw_fill_rate", "blsw_layout_io", "blsw_engine_submit_io", "blsw_verify_workspace_bytes", "blsw_verify_batch", "blsw_matrices_info_io", "blsw_matrices_fill_io",
                     "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch",
-                    "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate"]
+                    "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate", "blsw_layout_inputs",
+                    "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
 IO_MODES = {"witness": 0, "input": 1, "Witness": 0, "Input": 1}
 
 
-def layout(msg_len=32, params_mode=0, pk_mode=0, sig_mode=0):
+def layout(msg_len=32, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0):
     """Segment table of the witness vector (host logic; replaces cs.num_witness_variables(), constraints.rs:369-373).
     params_mode 1 / "witness": ParametersVar::new_variable with AllocationMode::Witness (constraints.rs:198-211).
     pk_mode / sig_mode 1 / "input": PublicKeyVar / SignatureVar::new_variable with AllocationMode::Input (constraints.rs:214-249): the point's
-    coordinates are public inputs (n_instance_vars > 1), its allocation segment is empty."""
+    coordinates are public inputs (n_instance_vars > 1), its allocation segment is empty.
+    msg_mode 1 / "input": UInt8::new_input_vec (constraints.rs:341 with AllocationMode::Input; blsw_layout_inputs): the message is
+    msg_input_chunks(msg_len) public inputs in front of the key's and the signature's, its segment 761 witnesses per chunk."""
     L = blsw_layout_t()
     params_mode = PARAMS_MODES.get(params_mode, params_mode)
-    pk_mode, sig_mode = IO_MODES.get(pk_mode, pk_mode), IO_MODES.get(sig_mode, sig_mode)
-    if pk_mode or sig_mode:
+    pk_mode, sig_mode, msg_mode = IO_MODES.get(pk_mode, pk_mode), IO_MODES.get(sig_mode, sig_mode), IO_MODES.get(msg_mode, msg_mode)
+    if msg_mode:
+        if params_mode:
+            raise BlswError("msg_mode Input applies to the circuit with Constant parameters")
+        rc = lib().blsw_layout_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(L))
+    elif pk_mode or sig_mode:
         if params_mode:
             raise BlswError("pk_mode / sig_mode Input apply to the circuit with Constant parameters")
         rc = lib().blsw_layout_io(msg_len, pk_mode, sig_mode, ctypes.byref(L))
@@ -160,6 +170,14 @@ def layout(msg_len=32, params_mode=0, pk_mode=0, sig_mode=0):
     if rc:
         raise BlswError("blsw_layout failed: %d" % rc)
     return {n: getattr(L, n) for n in _LAYOUT_FIELDS}
+
+
+MSG_CHUNK_BYTES = 47  # UInt8::new_input_vec: bytes per public input, (MODULUS_BIT_SIZE - 1) / 8
+
+
+def msg_input_chunks(msg_len):
+    """public inputs of a message of msg_len bytes allocated with UInt8::new_input_vec (= n_instance_vars - 1 - 3 pk_mode - 6 sig_mode)"""
+    return (int(msg_len) + MSG_CHUNK_BYTES - 1) // MSG_CHUNK_BYTES
 
 
 def engine_workspace_bytes(n, msg_len=32, max_steps=1, n_buffers=1):
@@ -208,7 +226,8 @@ def engine_options(**overrides):
     for var, field in (("BLSW_CHAIN_VARIANT", "chain_variant"), ("BLSW_COFACTOR_MODE", "cofactor_mode"), ("BLSW_EXPAND_VARIANT", "expand_variant"), ("BLSW_EXPAND_NT", "expand_store"), ("BLSW_PRIO_MODE", "prio_mode"), ("BLSW_PLACE_LDS", "place_lds"), ("BLSW_GROUP_RAMP", "group_ramp"), ("BLSW_LATENCY_MODE", "latency_mode")):
         if env.get(var):
             setattr(o, field, int(env[var]))
-    names = {"pairing_mode": {"team": 0, "lane": 1}, "g2_mode": {"lane": 0, "team": 1}, "params_mode": PARAMS_MODES, "pk_mode": IO_MODES, "sig_mode": IO_MODES}
+    names = {"pairing_mode": {"team": 0, "lane": 1}, "g2_mode": {"lane": 0, "team": 1}, "params_mode": PARAMS_MODES, "pk_mode": IO_MODES, "sig_mode": IO_MODES,
+             "msg_mode": IO_MODES}
     for k, v in overrides.items():
         if v is None:
             continue
@@ -235,7 +254,9 @@ class WitnessEngine:
         opt.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.n_keys = int(opt.n_keys)
         self.n_pairs = int(opt.n_pairs) if opt.n_pairs > 1 else 1
-        self.layout = layout_aggregate(msg_len, self.n_keys) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else layout(msg_len, int(opt.params_mode), int(opt.pk_mode), int(opt.sig_mode)))
+        self.msg_mode = int(opt.msg_mode)
+        self.layout = layout_aggregate(msg_len, self.n_keys) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else
+                                                                                  layout(msg_len, int(opt.params_mode), int(opt.pk_mode), int(opt.sig_mode), self.msg_mode))
         self.n_witness = self.layout["n_witness"]
         self.n_instance_vars = self.layout["n_instance_vars"]
         wb = ctypes.c_uint64(0)
@@ -275,7 +296,7 @@ class WitnessEngine:
 
     def submit(self, pk_xy, sig_xy, msg, witness=None, result=None, stream=None, instance=None):
         """-> step number (0, 1, 2, ... in submission order). instance: [n, n_instance_vars, 6] tensor that receives instance_assignment
-        (blsw_engine_submit_io; pk_mode / sig_mode Input engines: the public inputs an arkworks verifier takes)."""
+        (blsw_engine_submit_io; msg_mode / pk_mode / sig_mode Input engines: the public inputs an arkworks verifier takes)."""
         assert pk_xy.is_cuda and sig_xy.is_cuda and msg.is_cuda
         assert pk_xy.shape == (self.n, 12) and sig_xy.shape == (self.n, 24) and msg.shape == (self.n, self.msg_len)
         assert pk_xy.is_contiguous() and sig_xy.is_contiguous() and msg.is_contiguous()
@@ -516,15 +537,37 @@ class SignatureVar:
         return cls(xy, "Input")
 
 
+class UInt8:
+    """The message of constraints.rs:341 with its AllocationMode: `bytes` is an [n, msg_len] uint8 tensor. new_witness_vec (the reference's circuits;
+    a bare tensor passed to BlsSignatureVerifyGadget.verify means this) or new_input_vec (ark-r1cs-std 0.4.0: each 47-byte chunk is one public
+    input, its to_bits_le the witnesses the bytes are made of; the gadget's circuit must be msg_mode="input")."""
+
+    def __init__(self, bytes, mode="Witness"):
+        if mode not in ("Witness", "Input"):
+            raise BlswError("UInt8: AllocationMode %r is not on the GPU path (Witness or Input)" % (mode,))
+        self.bytes = bytes
+        self.mode = mode
+
+    @classmethod
+    def new_witness_vec(cls, msg):
+        return cls(msg)
+
+    @classmethod
+    def new_input_vec(cls, msg):
+        return cls(msg, "Input")
+
+
 class BlsSignatureVerifyGadget:
     """Batched counterpart of constraints.rs:79-128. One call = n independent circuits (direct mode engine, one batch)."""
 
     def __init__(self, n, msg_len=32, device=None, want_witness=True, max_steps=1, **options):
-        """options: blsw_engine_options_t fields; params_mode="witness" builds the circuit for ParametersVar.new_witness(), pk_mode / sig_mode="input" the
-        one for PublicKeyVar.new_input / SignatureVar.new_input (self.instance then holds every instance's instance_assignment after verify)."""
+        """options: blsw_engine_options_t fields; params_mode="witness" builds the circuit for ParametersVar.new_witness(), pk_mode / sig_mode / msg_mode="input"
+        the one for PublicKeyVar.new_input / SignatureVar.new_input / UInt8.new_input_vec (self.instance then holds every instance's instance_assignment
+        after verify)."""
         reserve = 0
         if want_witness and not options.get("n_keys") and not options.get("n_pairs"):
-            reserve = n * layout(msg_len, PARAMS_MODES.get(options.get("params_mode"), options.get("params_mode") or 0), options.get("pk_mode") or 0, options.get("sig_mode") or 0)["n_witness"] * 48
+            reserve = n * layout(msg_len, PARAMS_MODES.get(options.get("params_mode"), options.get("params_mode") or 0), options.get("pk_mode") or 0, options.get("sig_mode") or 0,
+                                 options.get("msg_mode") or 0)["n_witness"] * 48
         self.engine = WitnessEngine(n, msg_len, max_steps=max_steps, device=device, reserve_bytes=reserve, **options)
         torch = self.engine.torch
         self.torch = torch
@@ -536,14 +579,18 @@ class BlsSignatureVerifyGadget:
         self.instance = self.engine.new_instance_tensor() if self.layout["n_instance_vars"] > 1 else None
 
     def verify(self, parameters, public_key, message, signature, witness=None, stream=None):
-        """message: [n, msg_len] uint8 tensor. Returns the int32 result tensor (gadget Boolean per instance); the witness
-        vectors are in self.witness (or the tensor passed as `witness`)."""
+        """message: [n, msg_len] uint8 tensor (UInt8::new_witness_vec) or a UInt8 vector. Returns the int32 result tensor (gadget Boolean per instance);
+        the witness vectors are in self.witness (or the tensor passed as `witness`)."""
         assert isinstance(parameters, ParametersVar)
         if (parameters.mode == "Witness") != bool(self.layout["params_mode"]):
             raise BlswError("ParametersVar mode %s does not match the circuit this gadget was built for (params_mode=%d)" % (parameters.mode, self.layout["params_mode"]))
         for var, field in ((public_key, "pk_mode"), (signature, "sig_mode")):
             if (getattr(var, "mode", "Witness") == "Input") != bool(self.layout[field]):
                 raise BlswError("%s allocated as %s does not match the circuit this gadget was built for (%s=%d)" % (type(var).__name__, var.mode, field, self.layout[field]))
+        msg_var = message if isinstance(message, UInt8) else UInt8(message)
+        if (msg_var.mode == "Input") != bool(self.engine.msg_mode):
+            raise BlswError("UInt8 vector allocated as %s does not match the circuit this gadget was built for (msg_mode=%d)" % (msg_var.mode, self.engine.msg_mode))
+        message = msg_var.bytes
         w = witness if witness is not None else self.witness
         self.engine.submit(public_key.xy, signature.xy, message, witness=w, result=self.result, stream=stream, instance=self.instance)
         self.engine.flush(stream=stream)
@@ -559,6 +606,8 @@ def verify_mixed_lengths(parameters, public_key, messages, signature, want_witne
     or None with want_witness=False. layout(len(messages[i])) / matrices(len(messages[i])) describe instance i's system."""
     torch = _require_cuda()
     assert isinstance(parameters, ParametersVar)
+    if IO_MODES.get(options.get("msg_mode"), options.get("msg_mode")):
+        raise BlswError("verify_mixed_lengths: msg_mode Input is not offered (a batch's instance vectors would differ in length)")
     pk, sig = public_key.xy, signature.xy
     n = pk.shape[0]
     if len(messages) != n or sig.shape[0] != n:
@@ -727,17 +776,21 @@ def aggregate_verify(parameters, public_keys, bitmap, message, signature, want_w
     return res, cnt, wit
 
 
-def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0):
+def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0):
     """Constraint matrices of a circuit shape (host only; blsw_matrices_info + blsw_matrices_fill): the R1CS an arkworks prover
     takes next to the witness vectors, in ConstraintMatrices shape. Returns dict(n_constraints, n_instance_vars, n_witness,
     A / B / C = (row_ptr uint64 [n_constraints + 1], col uint32 [nnz], val uint64 [nnz, 6] Montgomery limbs)).
-    params_mode 1 / "witness" (single-key circuit): the system of layout(msg_len, params_mode=1)."""
+    params_mode 1 / "witness" (single-key circuit): the system of layout(msg_len, params_mode=1); msg_mode / pk_mode / sig_mode as layout()."""
     import numpy as np
 
     params_mode = PARAMS_MODES.get(params_mode, params_mode)
-    pk_mode, sig_mode = IO_MODES.get(pk_mode, pk_mode), IO_MODES.get(sig_mode, sig_mode)
+    pk_mode, sig_mode, msg_mode = IO_MODES.get(pk_mode, pk_mode), IO_MODES.get(sig_mode, sig_mode), IO_MODES.get(msg_mode, msg_mode)
     info = blsw_matrices_info_t()
-    if pk_mode or sig_mode:  # columns: 0 = one, 1 .. n_instance_vars - 1 = the public inputs, n_instance_vars + k = witness k
+    if msg_mode:  # columns: 0 = one, the message chunks, the key's and the signature's inputs, then the witnesses
+        if n_keys or n_pairs != 1 or params_mode:
+            raise BlswError("msg_mode applies to the single-key circuit with Constant parameters")
+        rc = lib().blsw_matrices_info_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(info))
+    elif pk_mode or sig_mode:  # columns: 0 = one, 1 .. n_instance_vars - 1 = the public inputs, n_instance_vars + k = witness k
         if n_keys or n_pairs != 1 or params_mode:
             raise BlswError("pk_mode / sig_mode apply to the single-key circuit with Constant parameters")
         rc = lib().blsw_matrices_info_io(msg_len, pk_mode, sig_mode, ctypes.byref(info))
@@ -758,7 +811,9 @@ def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode
         out.row_ptr[m] = rp[m].ctypes.data_as(u64p)
         out.col[m] = col[m].ctypes.data_as(u32p)
         out.val[m] = val[m].ctypes.data_as(u64p)
-    if pk_mode or sig_mode:
+    if msg_mode:
+        rc = lib().blsw_matrices_fill_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(info), ctypes.byref(out))
+    elif pk_mode or sig_mode:
         rc = lib().blsw_matrices_fill_io(msg_len, pk_mode, sig_mode, ctypes.byref(info), ctypes.byref(out))
     elif params_mode:
         rc = lib().blsw_matrices_fill_params(msg_len, params_mode, ctypes.byref(info), ctypes.byref(out))
@@ -803,10 +858,10 @@ class ConstraintChecker:
     public inputs), form 0 = Montgomery, 1 = canonical (options.output_form). The encoded matrices live in a device tensor this object
     owns; it is read-only after construction and recorded on every stream a call runs on."""
 
-    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None):
+    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None, msg_mode=0):
         torch = _require_cuda()
         self.torch = torch
-        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode)
+        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode, msg_mode)
         self.n_constraints, self.n_instance_vars, self.n_witness = int(mats["n_constraints"]), int(mats["n_instance_vars"]), int(mats["n_witness"])
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         if self.device.index is None:

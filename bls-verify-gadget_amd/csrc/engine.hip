@@ -368,6 +368,7 @@ static Group make_group(uint64_t steps, uint64_t n, uint32_t K, uint32_t msg_len
     g.n = (uint32_t)n;
     g.K = K;
     g.msg_len = msg_len;
+    g.msg_wit_len = msg_len;
     g.desc = desc;
     g.L = L;
     g.LS = L;
@@ -385,6 +386,7 @@ static int launch_group(blsw_engine* e) {
     // per-pair view: one lane per (instance, pair)
     Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->L, e->staged, e->modes, (uint64_t)steps * e->n));
     g.LS = e->LS;
+    if (e->opt.msg_mode) g.msg_wit_len = 0;  // UInt8::new_input_vec: k_msg_input writes the message segment, k_sha no message booleans
     g.chain_prio = e->opt.prio_mode == 0;
     g.canonical = (int)e->opt.output_form;
     // per-signature view (the same group for K == 1): the signature's chains and the Miller product on steps * n lanes
@@ -465,6 +467,7 @@ static int launch_group(blsw_engine* e) {
     } else  // one lane per key (per pair); params_mode: lanes [N, 2 N) allocate and prepare the generator (k_g1)
         hipLaunchKernelGGL(ck.g1, dim3(e->L.params_mode ? (unsigned)((2 * g.N + 63) / 64) : g1), dim3(64), 0, sb, g);
     hipEventRecord(b.ev_aux, sb);
+    if (e->opt.msg_mode && e->msg_len) hipLaunchKernelGGL(k_msg_input, dim3(g1), dim3(64), 0, sb, g);  // its inputs and the message segment
     if (e->L.sig_mode) {
         // SignatureVar::new_variable(Input): no allocation chain (prepare(sig) wrote the instance variables)
     } else if (e->modes.g2_team)
@@ -560,6 +563,8 @@ static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint3
     if (o->params_mode > 1 || (o->params_mode && (o->n_keys || o->n_pairs > 1 || o->pairing_mode))) return BLSW_ERR_ARG;
     // PublicKeyVar / SignatureVar allocated as public inputs: the single-key circuit with Constant parameters and the one-lane G2 kernels
     if (o->pk_mode > 1 || o->sig_mode > 1 || ((o->pk_mode || o->sig_mode) && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
+    // the message allocated as public inputs (UInt8::new_input_vec): the same circuits as pk_mode
+    if (o->msg_mode > 1 || (o->msg_mode && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
     return BLSW_OK;
 }
 
@@ -585,6 +590,12 @@ int blsw_layout_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, blsw_l
     return BLSW_OK;
 }
 
+int blsw_layout_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, blsw_layout_t* out) {
+    if (!out || msg_len > 65535 || msg_mode > 1 || pk_mode > 1 || sig_mode > 1) return BLSW_ERR_ARG;
+    make_layout(msg_len, out, 0, 1, false, pk_mode == 1, sig_mode == 1, msg_mode == 1);
+    return BLSW_OK;
+}
+
 int blsw_engine_options_default(blsw_engine_options_t* o) {
     if (!o) return BLSW_ERR_ARG;
     o->device = -1;
@@ -605,6 +616,7 @@ int blsw_engine_options_default(blsw_engine_options_t* o) {
     o->latency_mode = 0;
     o->pk_mode = 0;
     o->sig_mode = 0;
+    o->msg_mode = 0;
     return BLSW_OK;
 }
 
@@ -613,7 +625,7 @@ int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_st
     if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
     blsw_layout_t L;
     const uint32_t K = options->n_pairs > 1 ? options->n_pairs : 1;
-    make_layout(msg_len, &L, options->n_keys, K, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1);
+    make_layout(msg_len, &L, options->n_keys, K, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1, options->msg_mode == 1);
     const bool staged = max_steps > 1 || n_buffers > 1;
     // the same workspace serves every kernel variant: the largest carve of the three mode combinations
     uint64_t need = 0;
@@ -680,7 +692,8 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     e->staged = max_steps > 1 || n_buffers > 1;
     e->cofactor_mode = options->cofactor_mode;
     e->chains_inlined = options->chain_variant == 2 || (options->chain_variant == 0 && !e->staged);
-    make_layout(msg_len, &e->L, options->n_keys, options->n_pairs > 1 ? options->n_pairs : 1, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1);
+    make_layout(msg_len, &e->L, options->n_keys, options->n_pairs > 1 ? options->n_pairs : 1, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1,
+                options->msg_mode == 1);
     e->LS = e->L.n_pairs > 1 ? staging_layout_multi(e->L).LS : staging_layout(e->L, e->modes);
     for (int i = 0; i < BLSW_MAX_CONSUMED; i++) {
         e->consumed_ptr[i] = nullptr;

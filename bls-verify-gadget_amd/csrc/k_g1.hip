@@ -27,13 +27,14 @@ __global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_g1)(Group g) {
     }
     Proj<OpsFp> pk;
     if (g.L.pk_mode && !params) {
-        // PublicKeyVar::new_variable(Input) (constraints.rs:214-232) = new_variable_omit_prime_order_check: x, y, z are public inputs (1 .. 3 of
-        // instance_assignment), no witnesses, no in-circuit prime-order check
+        // PublicKeyVar::new_variable(Input) (constraints.rs:214-232) = new_variable_omit_prime_order_check: x, y, z are public inputs (after the
+        // message's, before the signature's: 1 + c .. 3 + c of instance_assignment for c message inputs), no witnesses, no in-circuit prime-order check
         const bool inf = fp_is_zero(x) && fp_is_zero(y);
         pk = {inf ? fp_zero() : x, inf ? fp_one() : y, inf ? fp_zero() : fp_one()};
-        put_instance(g, id, 1, pk.x);
-        put_instance(g, id, 2, pk.y);
-        put_instance(g, id, 3, pk.z);
+        const uint32_t k0 = g.L.n_instance_vars - 3 - (g.L.sig_mode ? 6 : 0);
+        put_instance(g, id, k0, pk.x);
+        put_instance(g, id, k0 + 1, pk.y);
+        put_instance(g, id, k0 + 2, pk.z);
     } else {
         pk = chain_g1_alloc_only(e_alloc, x, y);
     }

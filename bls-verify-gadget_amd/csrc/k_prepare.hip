@@ -19,11 +19,11 @@ __device__ __forceinline__ Proj<OpsFp2> prepare_point(const Group& g, const Lane
     }
     return q;
 }
-// SignatureVar::new_variable(Input) (constraints.rs:234-249): x, y, z (c0, c1 each) are public inputs after the key's; the prepare chain of the
-// signature is the kernel that has the point at hand (there is no allocation chain in this mode)
+// SignatureVar::new_variable(Input) (constraints.rs:234-249): x, y, z (c0, c1 each) are public inputs after the message's and the key's, the last six
+// of instance_assignment; the prepare chain of the signature is the kernel that has the point at hand (there is no allocation chain in this mode)
 __device__ __forceinline__ void put_sig_instance(const Group& g, const LaneId& id, const Proj<OpsFp2>& q) {
     if (!g.L.sig_mode || !item_leader()) return;
-    const uint32_t k0 = 1 + (g.L.pk_mode ? 3 : 0);
+    const uint32_t k0 = g.L.n_instance_vars - 6;
     put_instance(g, id, k0 + 0, q.x.c0);
     put_instance(g, id, k0 + 1, q.x.c1);
     put_instance(g, id, k0 + 2, q.y.c0);

@@ -13,9 +13,9 @@ __global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_sha)(Group g, int
     if (I >= g.N) return;
     LaneId id = lane_id(g, I);
     const uint8_t* msg = g.desc[id.s].msg + (uint64_t)id.f * g.msg_len;
-    // UInt8::new_witness_vec(msg): 8 booleans per byte, little-endian
+    // UInt8::new_witness_vec(msg): 8 booleans per byte, little-endian (none when the message is a public input: k_msg_input)
     Emitter em = EMITJ(g, id, off_msg, stride_msg);
-    for (uint32_t k = 0; k < g.msg_len; k++) {
+    for (uint32_t k = 0; k < g.msg_wit_len; k++) {
         uint32_t b = msg[k];
         for (int j = 0; j < 8; j++) em.put_bool((b >> j) & 1);
     }

@@ -249,6 +249,7 @@ struct Group {
     uint32_t n;   // instances per step
     uint32_t K;   // pairs per instance
     uint32_t msg_len;
+    uint32_t msg_wit_len;  // message bytes k_sha allocates as witness booleans: msg_len, or 0 when the message is a public input (k_msg_input)
     const StepDesc* desc;  // device array [steps]
     blsw_layout_t L;       // offsets in the witness vector
     blsw_layout_t LS;      // offsets in the staging rows (the vector with the SHA segment cut out)
@@ -401,6 +402,7 @@ __global__ void k_cofv_dbl_w(Group g);
 __global__ void k_cofv_add_w(Group g);
 __global__ void k_cofv_join(Group g);
 __global__ void k_sha_values(Group g);
+__global__ void k_msg_input(Group g);
 __global__ void k_map_values(Group g);
 __global__ void k_cofactor_values(Group g);
 __global__ void k_place_field(const Fp* __restrict__ staging, const Fp* __restrict__ pair, uint64_t first, uint32_t off_expand, uint32_t sha_bits,

@@ -21,7 +21,11 @@ enum : uint32_t {
     SEG_MILLER = 6826,       // 62 * 36 + 68 * (30 + 38) - 30
     SEG_FINAL_EXP = 7848,
     SEG_IS_ONE = 35,
+    SEG_MSG_CHUNK = 761,     // AllocatedFp::to_bits_le: 381 booleans + 380 AND witnesses of enforce_in_field_le
+    MSG_CHUNK_BYTES = 47,    // ToConstraintField<Fq> for [u8]: (MODULUS_BIT_SIZE - 1) / 8 bytes per field element
 };
+// public inputs of a message of msg_len bytes allocated with UInt8::new_input_vec
+BLSW_HD uint32_t msg_input_chunks(uint32_t msg_len) { return (msg_len + MSG_CHUNK_BYTES - 1) / MSG_CHUNK_BYTES; }
 
 // n_keys > 0: the aggregate_verify circuit (constraints.rs:378-441). n_pairs > 1: the N+1-pair product (one signature over
 // n_pairs (pk, msg) pairs; every statement of constraints.rs:97-125 becomes a loop over the pairs, allocation order
@@ -32,15 +36,19 @@ inline uint32_t seg_miller(uint32_t n_pairs) { return 62 * 36 + 68 * 30 - 30 + 6
 // and every ell of the (-g1, sig) pair has a variable point: 38 witnesses instead of 30, 2 instead of 0 in the first one (f = 1).
 // pk_input / sig_input: PublicKeyVar / SignatureVar::new_variable(Input) (constraints.rs:214-249), single-key circuit with Constant parameters only: the
 // point's coordinates are instance variables and its allocation segment is empty (no in-circuit prime-order check for public inputs).
+// msg_input: UInt8::new_input_vec (ark-r1cs-std 0.4.0), single-key circuit with Constant parameters only: the message is packed into
+// msg_input_chunks(msg_len) public inputs of MSG_CHUNK_BYTES bytes each, allocated before the key's and the signature's, and the message segment
+// holds each chunk's AllocatedFp::to_bits_le (SEG_MSG_CHUNK witnesses per chunk) instead of 8 booleans per byte.
 inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0, uint32_t n_pairs = 1, bool params_witness = false, bool pk_input = false,
-                        bool sig_input = false) {
+                        bool sig_input = false, bool msg_input = false) {
     std::vector<uint8_t> msg(msg_len ? msg_len : 1, 0);
     BitSink s;
     s.init(nullptr, 0);
     uint32_t uw[64];
     expand_message_w(s, msg.data(), msg_len, false, uw);
     L->msg_len = msg_len;
-    L->n_instance_vars = 1 + (pk_input ? 3 : 0) + (sig_input ? 6 : 0);
+    const uint32_t msg_chunks = msg_input ? msg_input_chunks(msg_len) : 0;
+    L->n_instance_vars = 1 + msg_chunks + (pk_input ? 3 : 0) + (sig_input ? 6 : 0);
     L->pk_mode = pk_input ? 1 : 0;
     L->sig_mode = sig_input ? 1 : 0;
     L->sha_bits = (uint32_t)s.nbits;
@@ -55,14 +63,14 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
     }
     const uint32_t K = n_keys ? 1 : (n_pairs ? n_pairs : 1);
     L->n_pairs = K;
-    L->stride_msg = 8 * msg_len;
+    L->stride_msg = msg_input ? SEG_MSG_CHUNK * msg_chunks : 8 * msg_len;
     L->stride_pk_alloc = pk_input ? 0 : SEG_PK_ALLOC;
     L->stride_pk_not_zero = SEG_PK_NOT_ZERO;
     L->stride_hash = L->sha_bits + 2 * SEG_MAP + SEG_ADD + SEG_COFACTOR;
     L->stride_prep_h = SEG_PREP_G2;
     L->stride_prep_pk = SEG_PREP_PK;
     L->off_msg = o;
-    o += 8 * msg_len * K;
+    o += L->stride_msg * K;
     L->params_mode = params_witness ? 1 : 0;
     L->off_params_alloc = L->off_prep_g1 = 0;
     if (params_witness) {

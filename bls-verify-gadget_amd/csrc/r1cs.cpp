@@ -1219,6 +1219,20 @@ static std::vector<U8> msg_alloc(uint32_t msg_len) {
     for (uint32_t i = 0; i < msg_len; i++) m[i] = u8_alloc();
     return m;
 }
+// UInt8::new_input_vec (ark-r1cs-std 0.4.0, ToConstraintField<Fq> for [u8] of ark-ff 0.4): chunks of MSG_CHUNK_BYTES bytes, each one public input
+// (AllocatedFp::new_input) followed by its to_bits_le; the bytes are bits [0, 8 * MSG_CHUNK_BYTES) of the chunks, concatenated and cut to 8 * msg_len
+// (UInt8::from_bits_le: no allocation)
+static std::vector<U8> msg_alloc_input(uint32_t msg_len) {
+    std::vector<B> bits;
+    for (uint32_t j = 0; j < msg_input_chunks(msg_len); j++) {
+        const std::vector<B> cb = v_to_bits_le(v_input());
+        bits.insert(bits.end(), cb.begin(), cb.begin() + 8 * MSG_CHUNK_BYTES);
+    }
+    std::vector<U8> m(msg_len);
+    for (uint32_t i = 0; i < msg_len; i++)
+        for (int k = 0; k < 8; k++) m[i].b[k] = bits[8 * i + k];
+    return m;
+}
 // verify over K (pk, msg) pairs and one signature (K = 1: constraints.rs:90-128 statement by statement)
 // g1: the generator variable of a ParametersVar allocated as witnesses (constraints.rs:198-211), or nullptr for Constant parameters
 static B verify_gadget(const std::vector<Pt<T1>>& pks, const std::vector<std::vector<U8>>& msgs, const Pt<T2>& sig, const Pt<T1>* g1 = nullptr) {
@@ -1235,7 +1249,8 @@ static B verify_gadget(const std::vector<Pt<T1>>& pks, const std::vector<std::ve
     V12 fe = final_exponentiation(miller_loop(ps, qs));
     return v12_is_eq(fe, v12_one());
 }
-static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool params_witness, bool pk_input = false, bool sig_input = false) {
+static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool params_witness, bool pk_input = false, bool sig_input = false,
+                    bool msg_input = false) {
     if (n_keys) {  // constraints.rs:378-441: keys, bitmap booleans, msg, params, sig, aggregate_verify
         std::vector<Pt<T1>> keys;
         for (uint32_t k = 0; k < n_keys; k++) keys.push_back(g1_new_witness());
@@ -1258,7 +1273,7 @@ static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool pa
         return;
     }
     std::vector<std::vector<U8>> msgs;
-    for (uint32_t j = 0; j < n_pairs; j++) msgs.push_back(msg_alloc(msg_len));
+    for (uint32_t j = 0; j < n_pairs; j++) msgs.push_back(msg_input ? msg_alloc_input(msg_len) : msg_alloc(msg_len));  // constraints.rs:341
     Pt<T1> g1 = pt_zero<T1>();
     if (params_witness) g1 = g1_new_witness();  // ParametersVar::new_variable(Witness): argument order of constraints.rs:346-364
     std::vector<Pt<T1>> pks;
@@ -1267,14 +1282,14 @@ static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool pa
     (void)verify_gadget(pks, msgs, sig, params_witness ? &g1 : nullptr);
 }
 
-// io_modes: bit 0 = pk Input, bit 1 = sig Input (single-key circuit with Constant parameters)
+// io_modes: bit 0 = pk Input, bit 1 = sig Input, bit 2 = msg Input (single-key circuit with Constant parameters)
 static int run(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, Sys& sys, uint32_t params_mode = 0, uint32_t io_modes = 0) {
     if (msg_len > 65535 || n_keys > 65535 || (n_keys && n_pairs > 1) || n_pairs == 0 || n_pairs > 4096) return BLSW_ERR_ARG;
     if (params_mode > 1 || (params_mode && (n_keys || n_pairs != 1))) return BLSW_ERR_ARG;
-    if (io_modes > 3 || (io_modes && (n_keys || n_pairs != 1 || params_mode))) return BLSW_ERR_ARG;
+    if (io_modes > 7 || (io_modes && (n_keys || n_pairs != 1 || params_mode))) return BLSW_ERR_ARG;
     S = &sys;
-    sys.n_inst = 1 + ((io_modes & 1) ? 3 : 0) + ((io_modes & 2) ? 6 : 0);
-    circuit(msg_len, n_keys, n_pairs, params_mode == 1, (io_modes & 1) != 0, (io_modes & 2) != 0);
+    sys.n_inst = 1 + ((io_modes & 4) ? msg_input_chunks(msg_len) : 0) + ((io_modes & 1) ? 3 : 0) + ((io_modes & 2) ? 6 : 0);
+    circuit(msg_len, n_keys, n_pairs, params_mode == 1, (io_modes & 1) != 0, (io_modes & 2) != 0, (io_modes & 4) != 0);
     sys.finish();
     S = nullptr;
     return BLSW_OK;
@@ -1373,5 +1388,13 @@ int blsw_matrices_info_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode,
 int blsw_matrices_fill_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
     if (pk_mode > 1 || sig_mode > 1) return BLSW_ERR_ARG;
     return matrices_fill(msg_len, 0, 1, 0, info, out, pk_mode | sig_mode << 1);
+}
+int blsw_matrices_info_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, blsw_matrices_info_t* out) {
+    if (msg_mode > 1 || pk_mode > 1 || sig_mode > 1) return BLSW_ERR_ARG;
+    return matrices_info(msg_len, 0, 1, 0, out, pk_mode | sig_mode << 1 | msg_mode << 2);
+}
+int blsw_matrices_fill_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
+    if (msg_mode > 1 || pk_mode > 1 || sig_mode > 1) return BLSW_ERR_ARG;
+    return matrices_fill(msg_len, 0, 1, 0, info, out, pk_mode | sig_mode << 1 | msg_mode << 2);
 }
 }

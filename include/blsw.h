@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 11
+#define BLSW_ABI_VERSION 12
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -45,7 +45,8 @@ extern "C" {
  * 36 uint32_t fields; the Rust mirror in INTEGRATION.md must have the same fields in the same order. */
 typedef struct {
     uint32_t msg_len;
-    uint32_t n_instance_vars; /* instance_assignment length: 1 (the constant one) + 3 if pk_mode is Input + 6 if sig_mode is Input */
+    uint32_t n_instance_vars; /* instance_assignment length: 1 (the constant one) + c message chunks if the message is Input (blsw_layout_inputs)
+                               * + 3 if pk_mode is Input + 6 if sig_mode is Input */
     uint32_t n_witness;       /* witness_assignment length */
     uint32_t sha_bits;        /* boolean witnesses of ONE expand_message segment (16 lib_str bits + SHA-256 gadget) */
     uint32_t off_msg, off_pk_alloc, off_sig_alloc, off_pk_not_zero, off_expand, off_map0, off_map1, off_add, off_cofactor, off_prep_h, off_prep_pk,
@@ -65,7 +66,10 @@ typedef struct {
      * reference's circuits), 1 = Input: the point's x, y, z are public inputs — instance_assignment = [1, pk.x, pk.y, pk.z, sig.x.c0, sig.x.c1,
      * sig.y.c0, sig.y.c1, sig.z.c0, sig.z.c1] in allocation order — and its allocation segment is empty (ark-r1cs-std 0.4.0 allocates Input points
      * through new_variable_omit_prime_order_check: no in-circuit subgroup check, a verifier checks its public inputs itself). Matrix columns:
-     * 0 = one, 1 .. n_instance_vars - 1 = the inputs, n_instance_vars + k = witness k. */
+     * 0 = one, 1 .. n_instance_vars - 1 = the inputs, n_instance_vars + k = witness k.
+     * The message allocated with UInt8::new_input_vec (blsw_layout_inputs, msg_mode 1) has no field of its own here: it comes first, as
+     * c = ceil(msg_len / 47) public inputs, and the caller recovers c as n_instance_vars - 1 - 3 * pk_mode - 6 * sig_mode. Its segment is then
+     * stride_msg = 761 * c witnesses instead of 8 * msg_len. */
     uint32_t pk_mode, sig_mode;
 } blsw_layout_t;
 
@@ -103,6 +107,14 @@ int blsw_layout_params(uint32_t msg_len, uint32_t params_mode, blsw_layout_t* ou
  * (blsw_layout_t.pk_mode). AllocationMode::Constant for a key or a signature is a different circuit in four segments and is not offered: BLSW_ERR_ARG.
  * Parameters Constant. Host only. */
 int blsw_layout_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, blsw_layout_t* out);
+/* ABI 12: blsw_layout_io with the message's allocation mode as well (src/constraints.rs:341): msg_mode 0 = UInt8::new_witness_vec (= blsw_layout_io),
+ * 1 = UInt8::new_input_vec (ark-r1cs-std 0.4.0; packing of ark-ff 0.4's ToConstraintField<Fq> for [u8]). The message is cut into c = ceil(msg_len / 47)
+ * chunks of 47 bytes (the last one may be shorter); chunk j, read as a little-endian integer (< 2^376 < p), is public input 1 + j — before the key's and
+ * the signature's: instance_assignment = [1, m_0 .. m_{c-1}, pk.x, pk.y, pk.z (pk_mode 1), sig.x.c0 .. sig.z.c1 (sig_mode 1)] — and its
+ * AllocatedFp::to_bits_le is the chunk's segment of 761 witnesses (381 booleans LSB first, then enforce_in_field_le's AND witnesses) at
+ * off_msg + 761 j. Byte k of the message is bits [8 k, 8 k + 8) of the chunks' low 376 bits concatenated (UInt8::from_bits_le: no variables). msg_len 0:
+ * c = 0, the msg_mode 0 circuit. Single-key circuit with Constant parameters, as pk_mode. Host only. */
+int blsw_layout_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, blsw_layout_t* out);
 int blsw_verify_multi_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_pairs, uint64_t* bytes);
 int blsw_verify_multi_batch(const uint64_t* d_pks_xy, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint64_t* d_sig_xy, uint64_t n,
                             uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, void* d_workspace, uint64_t workspace_bytes, void* stream);
@@ -177,6 +189,9 @@ typedef struct {
     uint32_t pk_mode;      /* PublicKeyVar allocation (src/constraints.rs:214-232): 0 (default) Witness, 1 Input (blsw_layout_io): batches go through
                               blsw_engine_submit_io, which also writes instance_assignment. Single-key circuit with Constant parameters only. */
     uint32_t sig_mode;     /* SignatureVar allocation (src/constraints.rs:234-249): 0 (default) Witness, 1 Input; as pk_mode; not with g2_mode 1 */
+    uint32_t msg_mode;     /* message allocation (src/constraints.rs:341, ABI 12): 0 (default) UInt8::new_witness_vec, 1 UInt8::new_input_vec (blsw_layout_inputs):
+                              blsw_engine_submit_io writes the message chunks into instance_assignment as well. Single-key circuit with Constant parameters
+                              and g2_mode 0 only, as pk_mode. */
 } blsw_engine_options_t;
 /* the defaults (pure: measurement scripts set the fields they want to vary). The one environment variable the library reads is the
  * diagnostic BLSW_TRACE_GROUP=1: an engine prints its launch groups' stage times to stderr at blsw_engine_destroy. */
@@ -197,7 +212,7 @@ int blsw_engine_create(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32
 int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
                           void* d_workspace, uint64_t workspace_bytes);
 int blsw_engine_destroy(blsw_engine_t* e);
-/* blsw_engine_submit for an engine with pk_mode / sig_mode Input (it works for every single-key engine): additionally writes
+/* blsw_engine_submit for an engine with msg_mode / pk_mode / sig_mode Input (it works for every single-key engine): additionally writes
  * d_instance [n][n_instance_vars][6] u64 = each instance's instance_assignment (element 0 = one; Montgomery limbs, or canonical integers with
  * options.output_form 1), i.e. what ConstraintSystem::instance_assignment holds after synthesis. d_instance may be NULL. */
 int blsw_engine_submit_io(blsw_engine_t* e, const uint64_t* d_pk_xy, const uint64_t* d_sig_xy, const uint8_t* d_msg, uint64_t* d_instance, uint64_t* d_witness,
@@ -327,6 +342,9 @@ int blsw_matrices_fill_params(uint32_t msg_len, uint32_t params_mode, const blsw
  * blsw_layout_t.pk_mode (ark-relations' ConstraintMatrices: instance variables first, then the witnesses) */
 int blsw_matrices_info_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, blsw_matrices_info_t* out);
 int blsw_matrices_fill_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out);
+/* the same for the circuit of blsw_layout_inputs (ABI 12); msg_mode 0 = the two calls above */
+int blsw_matrices_info_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, blsw_matrices_info_t* out);
+int blsw_matrices_fill_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out);
 
 /* Device R1CS evaluator (ABI 11): checks and evaluates the matrices above against witness vectors on the GPU — arkworks'
  * cs.is_satisfied() / cs.which_is_unsatisfied() and the A z, B z, C z a prover computes first, for n instances at a time.

@@ -6,7 +6,7 @@
 // One difference in shape, stated once: the reference builds ONE ConstraintSystemRef per (pk, msg, sig) instance and synthesises it on a CPU
 // thread; here a ConstraintSystem stands for n independent systems of one shape, generated together on the GPU. Everything else keeps its name:
 //   PublicKey::try_from / Signature::try_from          bls.rs:219-242, 316-339 (compressed ZCash encoding; decoded on the device)
-//   UInt8::new_witness_vec                              constraints.rs:341
+//   UInt8::new_witness_vec / new_input_vec              constraints.rs:341
 //   ParametersVar / PublicKeyVar / SignatureVar::new_variable(cs, value, AllocationMode)   constraints.rs:194-249
 //   BlsSignatureVerifyGadget::verify(&params, &pk, &msg, &sig) -> Boolean                  constraints.rs:90-128
 //   BlsSignatureVerifyGadget::aggregate_verify(&params, &keys, &bitmap, &msg, &sig) -> (Boolean, UInt32)   constraints.rs:153-191
@@ -166,8 +166,8 @@ class ConstraintSystem {
         witness_.download(w.data(), w.size() * 8, i * (size_t)layout_.n_witness * 48);
         return w;
     }
-    // instance_assignment of system i after verify: n_instance_vars elements (element 0 = one; then the coordinates of the points allocated with
-    // AllocationMode::Input, in allocation order), same element encoding as witness_assignment
+    // instance_assignment of system i after verify: n_instance_vars elements (element 0 = one; then the message chunks of UInt8::new_input_vec and
+    // the coordinates of the points allocated with AllocationMode::Input, in allocation order), same element encoding as witness_assignment
     std::vector<uint64_t> instance_assignment(size_t i) const {
         if (i >= n_) throw Error("instance_assignment out of range", BLSW_ERR_ARG);
         std::vector<uint64_t> v((size_t)layout_.n_instance_vars * 6);
@@ -185,6 +185,7 @@ class ConstraintSystem {
 
    private:
     friend class ParametersVar;
+    friend class UInt8;
     friend class PublicKeyVar;
     friend class SignatureVar;
     friend struct BlsSignatureVerifyGadget;
@@ -198,7 +199,8 @@ class ConstraintSystem {
     detail::DeviceBytes r1cs_buffer_;
     blsw_matrices_info_t matrices_info() const {
         blsw_matrices_info_t info;
-        check(layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
+        check(msg_mode_                          ? blsw_matrices_info_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info)
+              : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
               : layout_.params_mode              ? blsw_matrices_info_params(msg_len_, layout_.params_mode, &info)
                                                  : blsw_matrices_info(msg_len_, layout_.n_keys, 1, &info),
               "blsw_matrices_info");
@@ -217,7 +219,8 @@ class ConstraintSystem {
             m.col[k] = col[k].data();
             m.val[k] = val[k].data();
         }
-        check(layout_.pk_mode || layout_.sig_mode ? blsw_matrices_fill_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info, &m)
+        check(msg_mode_                          ? blsw_matrices_fill_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info, &m)
+              : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_fill_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info, &m)
               : layout_.params_mode              ? blsw_matrices_fill_params(msg_len_, layout_.params_mode, &info, &m)
                                                  : blsw_matrices_fill(msg_len_, layout_.n_keys, 1, &info, &m),
               "blsw_matrices_fill");
@@ -226,31 +229,49 @@ class ConstraintSystem {
         r1cs_buffer_ = detail::DeviceBytes(bytes);
         check(blsw_r1cs_create(&r1cs_, &info, &m, device_, r1cs_buffer_.get(), bytes, nullptr), "blsw_r1cs_create");
     }
-    // AllocationMode of the key / the signature: part of the circuit shape (blsw_layout_io)
-    void set_io(uint32_t pk_mode, uint32_t sig_mode) {
+    // AllocationMode of the message / the key / the signature: part of the circuit shape (blsw_layout_inputs). Each call states all three, so the
+    // shape is the same whatever order the new_variable / new_*_vec calls run in.
+    void set_io(uint32_t pk_mode, uint32_t sig_mode, uint32_t msg_mode) {
         if (engine_) throw Error("new_variable after verify", BLSW_ERR_ARG);
-        if ((pk_mode || sig_mode) && (layout_.params_mode || layout_.n_keys)) throw Error("AllocationMode::Input: the single-key circuit with Constant parameters", BLSW_ERR_ARG);
-        if (pk_mode || sig_mode || layout_.pk_mode || layout_.sig_mode) check(blsw_layout_io(msg_len_, pk_mode, sig_mode, &layout_), "blsw_layout_io");
+        if ((pk_mode || sig_mode || msg_mode) && (layout_.params_mode || layout_.n_keys))
+            throw Error("AllocationMode::Input: the single-key circuit with Constant parameters", BLSW_ERR_ARG);
+        if (pk_mode || sig_mode || msg_mode || layout_.pk_mode || layout_.sig_mode || msg_mode_)
+            check(blsw_layout_inputs(msg_len_, msg_mode, pk_mode, sig_mode, &layout_), "blsw_layout_inputs");
+        msg_mode_ = msg_mode;
     }
+    uint32_t msg_mode_ = 0;  // the message allocated with UInt8::new_input_vec (its chunks are instance_assignment[1 .. c])
     std::vector<int32_t> status_;
 };
 
-// constraints.rs:341: the message bytes of every system, allocated as witnesses (8 booleans per byte at the head of the vector)
+// constraints.rs:341: the message bytes of every system, allocated as witnesses (new_witness_vec: 8 booleans per byte at the head of the vector)
+// or as public inputs (new_input_vec: 47-byte chunks as instance variables, each decomposed into 761 witnesses; blsw_layout_inputs)
 class MessageVar {
    public:
     const std::vector<uint8_t>& bytes() const { return bytes_; }
+    bool is_input() const { return input_; }
 
    private:
     friend class UInt8;
     std::vector<uint8_t> bytes_;  // [n][msg_len]
+    bool input_ = false;
 };
 class UInt8 {
    public:
-    static MessageVar new_witness_vec(ConstraintSystem& cs, const std::vector<std::vector<uint8_t>>& msgs) {
-        if (msgs.size() != cs.num_instances()) throw Error("UInt8::new_witness_vec: one message per system", BLSW_ERR_ARG);
+    static MessageVar new_witness_vec(ConstraintSystem& cs, const std::vector<std::vector<uint8_t>>& msgs) { return make(cs, msgs, false); }
+    // ark-r1cs-std 0.4.0 UInt8::new_input_vec: fixes the message's mode in the circuit shape of `cs`
+    static MessageVar new_input_vec(ConstraintSystem& cs, const std::vector<std::vector<uint8_t>>& msgs) {
+        MessageVar m = make(cs, msgs, true);
+        cs.set_io(cs.layout_.pk_mode, cs.layout_.sig_mode, 1);
+        return m;
+    }
+
+   private:
+    static MessageVar make(ConstraintSystem& cs, const std::vector<std::vector<uint8_t>>& msgs, bool input) {
+        if (msgs.size() != cs.num_instances()) throw Error("UInt8::new_*_vec: one message per system", BLSW_ERR_ARG);
         MessageVar m;
+        m.input_ = input;
         for (auto& x : msgs) {
-            if (x.size() != cs.msg_len()) throw Error("UInt8::new_witness_vec: message length != the circuit's", BLSW_ERR_ARG);
+            if (x.size() != cs.msg_len()) throw Error("UInt8::new_*_vec: message length != the circuit's", BLSW_ERR_ARG);
             m.bytes_.insert(m.bytes_.end(), x.begin(), x.end());
         }
         return m;
@@ -264,8 +285,8 @@ class ParametersVar {
         if (mode == AllocationMode::Input) throw Error("ParametersVar: AllocationMode::Input (instance variables are not produced)", BLSW_ERR_ARG);
         if (cs.engine_) throw Error("ParametersVar::new_variable after verify", BLSW_ERR_ARG);
         // the allocation modes together fix the circuit shape, whatever the order the three new_variable calls run in (C++ argument evaluation order)
-        if (cs.layout_.pk_mode || cs.layout_.sig_mode) {
-            if (mode == AllocationMode::Witness) throw Error("ParametersVar: AllocationMode::Witness together with Input keys / signatures", BLSW_ERR_ARG);
+        if (cs.layout_.pk_mode || cs.layout_.sig_mode || cs.msg_mode_) {
+            if (mode == AllocationMode::Witness) throw Error("ParametersVar: AllocationMode::Witness together with Input messages / keys / signatures", BLSW_ERR_ARG);
         } else {
             check(blsw_layout_params(cs.msg_len_, mode == AllocationMode::Witness ? 1u : 0u, &cs.layout_), "blsw_layout_params");
         }
@@ -285,7 +306,7 @@ class PublicKeyVar {
     static PublicKeyVar new_variable(ConstraintSystem& cs, const std::vector<PublicKey>& keys, AllocationMode mode) {
         if (mode == AllocationMode::Constant) throw Error("PublicKeyVar: AllocationMode::Constant is not on the GPU path", BLSW_ERR_ARG);
         if (keys.size() != cs.num_instances()) throw Error("PublicKeyVar::new_variable: one key per system", BLSW_ERR_ARG);
-        cs.set_io(mode == AllocationMode::Input ? 1u : 0u, cs.layout_.sig_mode);
+        cs.set_io(mode == AllocationMode::Input ? 1u : 0u, cs.layout_.sig_mode, cs.msg_mode_);
         PublicKeyVar v;
         v.keys_ = keys;
         return v;
@@ -300,7 +321,7 @@ class SignatureVar {
     static SignatureVar new_variable(ConstraintSystem& cs, const std::vector<Signature>& sigs, AllocationMode mode) {
         if (mode == AllocationMode::Constant) throw Error("SignatureVar: AllocationMode::Constant is not on the GPU path", BLSW_ERR_ARG);
         if (sigs.size() != cs.num_instances()) throw Error("SignatureVar::new_variable: one signature per system", BLSW_ERR_ARG);
-        cs.set_io(cs.layout_.pk_mode, mode == AllocationMode::Input ? 1u : 0u);
+        cs.set_io(cs.layout_.pk_mode, mode == AllocationMode::Input ? 1u : 0u, cs.msg_mode_);
         SignatureVar v;
         v.sigs_ = sigs;
         return v;
@@ -347,6 +368,7 @@ struct BlsSignatureVerifyGadget {
             throw Error("verify: variables of another ConstraintSystem", BLSW_ERR_ARG);
         // one circuit shape per ConstraintSystem: aggregate_verify has replaced the layout (num_witness_variables would be the aggregate circuit's)
         if (cs.layout_.n_keys) throw Error("verify: this ConstraintSystem was synthesised by aggregate_verify; use a new one", BLSW_ERR_ARG);
+        if (message.is_input() != (cs.msg_mode_ == 1)) throw Error("verify: the message's AllocationMode is not the one of this ConstraintSystem's circuit", BLSW_ERR_ARG);
         if (!cs.engine_) {
             blsw_engine_options_t opt;
             check(blsw_engine_options_default(&opt), "blsw_engine_options_default");
@@ -354,6 +376,7 @@ struct BlsSignatureVerifyGadget {
             opt.params_mode = cs.layout_.params_mode;
             opt.pk_mode = cs.layout_.pk_mode;
             opt.sig_mode = cs.layout_.sig_mode;
+            opt.msg_mode = cs.msg_mode_;
             uint64_t bytes = 0;
             check(blsw_engine_workspace_bytes_ex(n, cs.msg_len_, 1, 1, &opt, &bytes), "blsw_engine_workspace_bytes_ex");
             if (cs.device_ >= 0) hip_check(hipSetDevice(cs.device_), "hipSetDevice");
@@ -375,7 +398,7 @@ struct BlsSignatureVerifyGadget {
         d_pk.upload(pk.data(), pk.size());
         d_sg.upload(sg.data(), sg.size());
         if (!message.bytes().empty()) d_msg.upload(message.bytes().data(), message.bytes().size());
-        const bool io = cs.layout_.pk_mode || cs.layout_.sig_mode;
+        const bool io = cs.layout_.pk_mode || cs.layout_.sig_mode || cs.msg_mode_;
         if (io) {  // public inputs: decode, then the step that also writes instance_assignment; the fallback rule of tests/tests.rs:244-263 is applied below
             check(blsw_decode_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), n, static_cast<uint64_t*>(cs.pk_xy_.get()),
                                     static_cast<uint64_t*>(cs.sig_xy_.get()), static_cast<int32_t*>(cs.d_status_.get()), nullptr),

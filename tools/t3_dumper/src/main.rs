@@ -9,8 +9,10 @@
 //! and prints the first segment that differs. With `--params-witness` it does the same for the golden file's "params_witness" section:
 //! the circuit with `ParametersVar::new_variable(.., AllocationMode::Witness)` (src/constraints.rs:198-211 takes any mode). With `--pk-input` and / or
 //! `--sig-input` it checks the "public_inputs" sections: `PublicKeyVar` / `SignatureVar::new_variable(.., AllocationMode::Input)`
-//! (src/constraints.rs:214-249), where cs.instance_assignment (digest `sha256_instance`) carries the point's coordinates. Written for this
-//! repository; not derived from the reference's sources beyond calling its public API.
+//! (src/constraints.rs:214-249), where cs.instance_assignment (digest `sha256_instance`) carries the point's coordinates. With `--msg-input`
+//! the message is allocated with `UInt8::new_input_vec` (ABI 12, options.msg_mode 1: 47-byte chunks as public inputs in front of the key's and
+//! the signature's) and the cases come from the golden file's "msg_input" section, keyed like "public_inputs" (pk_witness_sig_witness, ...);
+//! `--pk-input` / `--sig-input` combine with it. Written for this repository; not derived from the reference's sources beyond calling its public API.
 use ark_bls12_381::{Config, Fq};
 use ark_crypto_primitives::signature::SigVerifyGadget;
 use ark_r1cs_std::alloc::AllocVar;
@@ -38,13 +40,17 @@ fn main() {
     let params_witness = args.iter().any(|a| a == "--params-witness");
     let pk_input = args.iter().any(|a| a == "--pk-input");
     let sig_input = args.iter().any(|a| a == "--sig-input");
-    let path = args.iter().find(|a| !a.starts_with("--")).expect("usage: t3-dumper [--params-witness | --pk-input | --sig-input] <witness_digests.json>");
+    let msg_input = args.iter().any(|a| a == "--msg-input");
+    let path = args
+        .iter()
+        .find(|a| !a.starts_with("--"))
+        .expect("usage: t3-dumper [--params-witness | [--msg-input] [--pk-input] [--sig-input]] <witness_digests.json>");
     let file: serde_json::Value = serde_json::from_str(&std::fs::read_to_string(path).unwrap()).unwrap();
     let golden = if params_witness {
         file["params_witness"].clone()
-    } else if pk_input || sig_input {
+    } else if msg_input || pk_input || sig_input {
         let key = format!("pk_{}_sig_{}", if pk_input { "input" } else { "witness" }, if sig_input { "input" } else { "witness" });
-        file["public_inputs"][key.as_str()].clone()
+        file[if msg_input { "msg_input" } else { "public_inputs" }][key.as_str()].clone()
     } else {
         file
     };
@@ -57,7 +63,7 @@ fn main() {
         let pk = PublicKey::<Config>::try_from(case["pubkey"].as_str().unwrap()).unwrap();
         let sig = Signature::<Config>::try_from(case["signature"].as_str().unwrap()).unwrap();
         let msg = hex::decode(case["message"].as_str().unwrap()).unwrap();
-        let msg_var = UInt8::<Fq>::new_witness_vec(cs.clone(), &msg).unwrap();
+        let msg_var = if msg_input { UInt8::<Fq>::new_input_vec(cs.clone(), &msg).unwrap() } else { UInt8::<Fq>::new_witness_vec(cs.clone(), &msg).unwrap() };
         let params = ParametersVar::<Config>::new_variable(cs.clone(), || Ok(Parameters::default()), params_mode).unwrap();
         let pk_var = PublicKeyVar::<Config>::new_variable(cs.clone(), || Ok(pk), pk_mode).unwrap();
         let sig_var = SignatureVar::<Config>::new_variable(cs.clone(), || Ok(sig), sig_mode).unwrap();
