@@ -29,7 +29,7 @@ class blsw_layout_t(ctypes.Structure):
 
 
 class blsw_engine_options_t(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode msg_mode".split()]
+    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode msg_mode agg_inputs".split()]
 
 
 class blsw_matrices_info_t(ctypes.Structure):
@@ -99,6 +99,10 @@ def lib():
         L.blsw_layout_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_layout_t)]
         L.blsw_matrices_info_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t)]
         L.blsw_matrices_fill_inputs.argtypes = [u32, u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
+        L.blsw_layout_aggregate_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_layout_t)]
+        L.blsw_matrices_info_aggregate_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t)]
+        L.blsw_matrices_fill_aggregate_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
+        L.blsw_engine_submit_aggregate_io.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
         L.blsw_layout_multi.argtypes = [u32, u32, ctypes.POINTER(blsw_layout_t)]
         L.blsw_verify_multi_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
         L.blsw_verify_multi_batch.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, vp, u64, vp]
@@ -140,11 +144,15 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_verify_multi_workspace_bytes", "blsw_verify_multi_batch", "blsw_matrices_info", "blsw_matrices_fill", "blsw_sign_batch", "blsw_microbench", "blsw_fill_rate", "blsw_layout_io", "blsw_engine_submit_io", "blsw_verify_workspace_bytes", "blsw_verify_batch", "blsw_matrices_info_io", "blsw_matrices_fill_io",
                     "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch",
                     "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate", "blsw_layout_inputs",
-                    "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs"]
+                    "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs", "blsw_layout_aggregate_inputs", "blsw_matrices_info_aggregate_inputs",
+                    "blsw_matrices_fill_aggregate_inputs", "blsw_engine_submit_aggregate_io"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
 IO_MODES = {"witness": 0, "input": 1, "Witness": 0, "Input": 1}
+
+
+AGG_KEYS_INPUT, AGG_BITMAP_INPUT, AGG_MSG_INPUT, AGG_SIG_INPUT = 1, 2, 4, 8  # include/blsw.h: BLSW_AGG_*_INPUT, the bits of agg_inputs
 
 
 def layout(msg_len=32, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0):
@@ -211,7 +219,7 @@ def check_capacity(device, what, *byte_counts):
 
 def engine_options(**overrides):
     """blsw_engine_options_default with keyword overrides: device, pairing_mode ("team"/"lane" or 0/1), g2_mode ("lane"/"team"
-    or 0/1), expand_variant, expand_store, prio_mode, place_lds, consumer_mode, output_form, n_keys. The library itself reads no
+    or 0/1), expand_variant, expand_store, prio_mode, place_lds, consumer_mode, output_form, n_keys, agg_inputs (mask of AGG_*_INPUT). The library itself reads no
     environment for its options (one diagnostic: BLSW_TRACE_GROUP=1 prints every launch group's stage times at engine destruction); for A/B runs of measurement scripts THIS function applies BLSW_PAIRING=lane, BLSW_G2=team, BLSW_EXPAND_VARIANT,
     BLSW_EXPAND_NT, BLSW_PRIO_MODE, BLSW_PLACE_LDS (explicit keyword arguments win)."""
     o = blsw_engine_options_t()
@@ -255,7 +263,8 @@ class WitnessEngine:
         self.n_keys = int(opt.n_keys)
         self.n_pairs = int(opt.n_pairs) if opt.n_pairs > 1 else 1
         self.msg_mode = int(opt.msg_mode)
-        self.layout = layout_aggregate(msg_len, self.n_keys) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else
+        self.agg_inputs = int(opt.agg_inputs)
+        self.layout = layout_aggregate(msg_len, self.n_keys, self.agg_inputs) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else
                                                                                   layout(msg_len, int(opt.params_mode), int(opt.pk_mode), int(opt.sig_mode), self.msg_mode))
         self.n_witness = self.layout["n_witness"]
         self.n_instance_vars = self.layout["n_instance_vars"]
@@ -373,20 +382,27 @@ class WitnessEngine:
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq
 
-    def submit_aggregate(self, pks_xy, bitmap, sig_xy, msg, witness=None, result=None, count=None, stream=None):
-        """aggregate_verify batch (engine created with n_keys=K): pks_xy [n, K, 12] int64, bitmap [n, K] uint8 -> step number"""
+    def submit_aggregate(self, pks_xy, bitmap, sig_xy, msg, witness=None, result=None, count=None, stream=None, instance=None):
+        """aggregate_verify batch (engine created with n_keys=K): pks_xy [n, K, 12] int64, bitmap [n, K] uint8 -> step number.
+        instance: [n, n_instance_vars, 6] tensor that receives instance_assignment (blsw_engine_submit_aggregate_io; agg_inputs engines: the
+        keys, bitmap bits, message chunks and signature an arkworks verifier takes as public inputs, in that order)."""
         K = self.n_keys
         assert K and pks_xy.shape == (self.n, K, 12) and bitmap.shape == (self.n, K) and sig_xy.shape == (self.n, 24) and msg.shape == (self.n, self.msg_len)
         assert pks_xy.is_contiguous() and bitmap.is_contiguous() and sig_xy.is_contiguous() and msg.is_contiguous()
         if witness is not None:
             assert witness.is_contiguous() and witness.shape[0] == self.n and witness.shape[1] >= self.n_witness
         seq = self.submitted()
-        rc = lib().blsw_engine_submit_aggregate(self._e, pks_xy.data_ptr(), bitmap.data_ptr(), sig_xy.data_ptr(), msg.data_ptr() if self.msg_len else None,
-                                                witness.data_ptr() if witness is not None else None, witness.shape[1] if witness is not None else 0,
-                                                result.data_ptr() if result is not None else None, count.data_ptr() if count is not None else None, self._stream(stream))
+        tail = (witness.data_ptr() if witness is not None else None, witness.shape[1] if witness is not None else 0,
+                result.data_ptr() if result is not None else None, count.data_ptr() if count is not None else None, self._stream(stream))
+        if instance is not None:
+            assert instance.is_contiguous() and tuple(instance.shape) == (self.n, self.n_instance_vars, 6)
+            rc = lib().blsw_engine_submit_aggregate_io(self._e, pks_xy.data_ptr(), bitmap.data_ptr(), sig_xy.data_ptr(), msg.data_ptr() if self.msg_len else None,
+                                                       instance.data_ptr(), *tail)
+        else:
+            rc = lib().blsw_engine_submit_aggregate(self._e, pks_xy.data_ptr(), bitmap.data_ptr(), sig_xy.data_ptr(), msg.data_ptr() if self.msg_len else None, *tail)
         if rc:
             raise (BlswBusy if rc == ERR_BUSY else BlswError)("blsw_engine_submit_aggregate failed: %d" % rc)
-        self._keep.append((pks_xy, bitmap, sig_xy, msg, witness, result, count))
+        self._keep.append((pks_xy, bitmap, sig_xy, msg, witness, result, count, instance))
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq
 
@@ -555,6 +571,26 @@ class UInt8:
     @classmethod
     def new_input_vec(cls, msg):
         return cls(msg, "Input")
+
+
+class Boolean:
+    """A bit of aggregate_verify's bitmap (constraints.rs:414-419) with its AllocationMode: `bits` is an [n, K] uint8 tensor of 0 / 1. new_witness (the
+    reference's test; a bare tensor passed to aggregate_verify means this) or new_input (AllocatedBool::new_variable with Input: every bit is a public
+    input that keeps its booleanity constraint and has no witness)."""
+
+    def __init__(self, bits, mode="Witness"):
+        if mode not in ("Witness", "Input"):
+            raise BlswError("Boolean: AllocationMode %r is not on the GPU path (Witness or Input)" % (mode,))
+        self.bits = bits
+        self.mode = mode
+
+    @classmethod
+    def new_witness(cls, bits):
+        return cls(bits)
+
+    @classmethod
+    def new_input(cls, bits):
+        return cls(bits, "Input")
 
 
 class BlsSignatureVerifyGadget:
@@ -740,9 +776,13 @@ def verify_bytes_batch(pk48, msg, sig96):
     return res == 1
 
 
-def layout_aggregate(msg_len, n_keys):
+def layout_aggregate(msg_len, n_keys, agg_inputs=0):
+    """Segment table of the aggregate_verify circuit; agg_inputs: mask of AGG_*_INPUT (blsw_layout_aggregate_inputs), 0 = every argument Witness"""
     L = blsw_layout_t()
-    rc = lib().blsw_layout_aggregate(msg_len, n_keys, ctypes.byref(L))
+    if agg_inputs:
+        rc = lib().blsw_layout_aggregate_inputs(msg_len, n_keys, agg_inputs, ctypes.byref(L))
+    else:
+        rc = lib().blsw_layout_aggregate(msg_len, n_keys, ctypes.byref(L))
     if rc:
         raise BlswError("blsw_layout_aggregate failed: %d" % rc)
     return {n: getattr(L, n) for n in _LAYOUT_FIELDS}
@@ -750,13 +790,38 @@ def layout_aggregate(msg_len, n_keys):
 
 def aggregate_verify(parameters, public_keys, bitmap, message, signature, want_witness=True):
     """BlsSignatureVerifyGadget::aggregate_verify (constraints.rs:153-167) for n instances: public_keys.xy [n, K, 12] int64,
-    bitmap [n, K] uint8 (0/1), message [n, msg_len] uint8, signature.xy [n, 24]. Returns (result int32 [n], count int32 [n], witness)."""
+    bitmap [n, K] uint8 (0/1) or a Boolean vector, message [n, msg_len] uint8 or a UInt8 vector, signature.xy [n, 24].
+    Returns (result int32 [n], count int32 [n], witness). With an argument allocated as Input (PublicKeyVar.new_input, Boolean.new_input,
+    UInt8.new_input_vec, SignatureVar.new_input) the circuit is the one of layout_aggregate(msg_len, K, mask): a direct-mode engine runs it and
+    the call returns (result, count, witness, instance) with instance [n, n_instance_vars, 6] = every instance's instance_assignment."""
     torch = _require_cuda()
     assert isinstance(parameters, ParametersVar)
-    pks, sig, bitmap, message = public_keys.xy.contiguous(), signature.xy.contiguous(), bitmap.contiguous(), message.contiguous()
+    bit_var = bitmap if isinstance(bitmap, Boolean) else Boolean(bitmap)
+    msg_var = message if isinstance(message, UInt8) else UInt8(message)
+    mask = ((AGG_KEYS_INPUT if public_keys.mode == "Input" else 0) | (AGG_BITMAP_INPUT if bit_var.mode == "Input" else 0) |
+            (AGG_MSG_INPUT if msg_var.mode == "Input" else 0) | (AGG_SIG_INPUT if signature.mode == "Input" else 0))
+    pks, sig, bitmap, message = public_keys.xy.contiguous(), signature.xy.contiguous(), bit_var.bits.contiguous(), msg_var.bytes.contiguous()
     n, K = pks.shape[0], pks.shape[1]
     assert K >= 1 and bitmap.shape == (n, K)  # constraints.rs:160-162: equal lengths, at least one key
     msg_len = message.shape[1]
+    if mask:
+        if parameters.mode != "Constant":
+            raise BlswError("aggregate_verify with Input arguments: ParametersVar allocated as %s is not offered (Constant)" % parameters.mode)
+        assert sig.shape == (n, 24) and message.shape[0] == n
+        lay = layout_aggregate(msg_len, K, mask)
+        eng = WitnessEngine(n, msg_len, max_steps=1, n_buffers=1, device=pks.device, reserve_bytes=n * lay["n_witness"] * 48 if want_witness else 0, n_keys=K,
+                            agg_inputs=mask)
+        try:
+            res = torch.empty(n, dtype=torch.int32, device=pks.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=pks.device)
+            wit = eng.new_witness_tensor() if want_witness else None
+            inst = eng.new_instance_tensor()
+            eng.submit_aggregate(pks, bitmap, sig, message, witness=wit, result=res, count=cnt, instance=inst)
+            eng.flush()
+            torch.cuda.synchronize(pks.device)
+        finally:
+            eng.close()
+        return res, cnt, wit, inst
     lay = layout_aggregate(msg_len, K)
     wb = ctypes.c_uint64(0)
     lib().blsw_aggregate_workspace_bytes(n, msg_len, K, ctypes.byref(wb))
@@ -776,17 +841,23 @@ def aggregate_verify(parameters, public_keys, bitmap, message, signature, want_w
     return res, cnt, wit
 
 
-def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0):
+def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0, agg_inputs=0):
     """Constraint matrices of a circuit shape (host only; blsw_matrices_info + blsw_matrices_fill): the R1CS an arkworks prover
     takes next to the witness vectors, in ConstraintMatrices shape. Returns dict(n_constraints, n_instance_vars, n_witness,
     A / B / C = (row_ptr uint64 [n_constraints + 1], col uint32 [nnz], val uint64 [nnz, 6] Montgomery limbs)).
-    params_mode 1 / "witness" (single-key circuit): the system of layout(msg_len, params_mode=1); msg_mode / pk_mode / sig_mode as layout()."""
+    params_mode 1 / "witness" (single-key circuit): the system of layout(msg_len, params_mode=1); msg_mode / pk_mode / sig_mode as layout();
+    agg_inputs (with n_keys): the system of layout_aggregate(msg_len, n_keys, agg_inputs)."""
     import numpy as np
 
     params_mode = PARAMS_MODES.get(params_mode, params_mode)
     pk_mode, sig_mode, msg_mode = IO_MODES.get(pk_mode, pk_mode), IO_MODES.get(sig_mode, sig_mode), IO_MODES.get(msg_mode, msg_mode)
     info = blsw_matrices_info_t()
-    if msg_mode:  # columns: 0 = one, the message chunks, the key's and the signature's inputs, then the witnesses
+    if agg_inputs and (not n_keys or n_pairs != 1 or params_mode):
+        raise BlswError("agg_inputs applies to the aggregate_verify circuit (n_keys > 0)")
+    agg = bool(agg_inputs) and not (msg_mode or pk_mode or sig_mode)  # the three single-key modes stay refused together with n_keys, below
+    if agg:
+        rc = lib().blsw_matrices_info_aggregate_inputs(msg_len, n_keys, agg_inputs, ctypes.byref(info))
+    elif msg_mode:  # columns: 0 = one, the message chunks, the key's and the signature's inputs, then the witnesses
         if n_keys or n_pairs != 1 or params_mode:
             raise BlswError("msg_mode applies to the single-key circuit with Constant parameters")
         rc = lib().blsw_matrices_info_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(info))
@@ -811,7 +882,9 @@ def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode
         out.row_ptr[m] = rp[m].ctypes.data_as(u64p)
         out.col[m] = col[m].ctypes.data_as(u32p)
         out.val[m] = val[m].ctypes.data_as(u64p)
-    if msg_mode:
+    if agg:
+        rc = lib().blsw_matrices_fill_aggregate_inputs(msg_len, n_keys, agg_inputs, ctypes.byref(info), ctypes.byref(out))
+    elif msg_mode:
         rc = lib().blsw_matrices_fill_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(info), ctypes.byref(out))
     elif pk_mode or sig_mode:
         rc = lib().blsw_matrices_fill_io(msg_len, pk_mode, sig_mode, ctypes.byref(info), ctypes.byref(out))
@@ -858,10 +931,10 @@ class ConstraintChecker:
     public inputs), form 0 = Montgomery, 1 = canonical (options.output_form). The encoded matrices live in a device tensor this object
     owns; it is read-only after construction and recorded on every stream a call runs on."""
 
-    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None, msg_mode=0):
+    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None, msg_mode=0, agg_inputs=0):
         torch = _require_cuda()
         self.torch = torch
-        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode, msg_mode)
+        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode, msg_mode, agg_inputs)
         self.n_constraints, self.n_instance_vars, self.n_witness = int(mats["n_constraints"]), int(mats["n_instance_vars"]), int(mats["n_witness"])
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         if self.device.index is None:

@@ -5,6 +5,7 @@
 #include <map>
 #include <vector>
 #include "kcommon.hpp"
+#include "agg_input.hpp"
 
 using namespace blsw;
 
@@ -378,6 +379,17 @@ static Group make_group(uint64_t steps, uint64_t n, uint32_t K, uint32_t msg_len
     return g;
 }
 
+// the circuit an engine's options select (checked by check_options): the aggregate circuit takes its allocation modes from agg_inputs, the
+// single-key circuit and the N+1-pair product from params_mode / pk_mode / sig_mode / msg_mode
+static void options_layout(uint32_t msg_len, const blsw_engine_options_t* o, blsw_layout_t* L) {
+    if (o->n_keys)
+        make_layout_aggregate(msg_len, L, o->n_keys, o->agg_inputs);
+    else
+        make_layout(msg_len, L, 0, o->n_pairs > 1 ? o->n_pairs : 1, o->params_mode == 1, o->pk_mode == 1, o->sig_mode == 1, o->msg_mode == 1);
+}
+// is the message allocated with UInt8::new_input_vec?
+static bool options_msg_input(const blsw_engine_options_t* o) { return o->n_keys ? (o->agg_inputs & BLSW_AGG_MSG_INPUT) != 0 : o->msg_mode == 1; }
+
 static int launch_group(blsw_engine* e) {
     GroupBuf& b = e->buf[e->cur];
     const uint32_t steps = e->pending;
@@ -386,7 +398,8 @@ static int launch_group(blsw_engine* e) {
     // per-pair view: one lane per (instance, pair)
     Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->L, e->staged, e->modes, (uint64_t)steps * e->n));
     g.LS = e->LS;
-    if (e->opt.msg_mode) g.msg_wit_len = 0;  // UInt8::new_input_vec: k_msg_input writes the message segment, k_sha no message booleans
+    const bool msg_input = options_msg_input(&e->opt);
+    if (msg_input) g.msg_wit_len = 0;  // UInt8::new_input_vec: k_msg_input writes the message segment, k_sha no message booleans
     g.chain_prio = e->opt.prio_mode == 0;
     g.canonical = (int)e->opt.output_form;
     // per-signature view (the same group for K == 1): the signature's chains and the Miller product on steps * n lanes
@@ -461,13 +474,22 @@ static int launch_group(blsw_engine* e) {
     // only the end of the group waits for (ev_side): the longest aux kernel no longer delays the pairing of a latency-bound group
     hipStream_t sb = b.st[1];
     launch_prepare(ck, vf, gs, 1, sb);
-    if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
+    if (e->L.n_keys && e->L.pk_mode) {  // aggregate_verify with the keys as public inputs: nothing allocates them
+        hipLaunchKernelGGL(ck.agg_sum_in, dim3(g1), dim3(64), 0, sb, g);
+    } else if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
         hipLaunchKernelGGL(ck.agg_keys, dim3((unsigned)((g.N * e->L.n_keys + 63) / 64)), dim3(64), 0, sb, g, g.ws.keyproj);
         hipLaunchKernelGGL(ck.agg_sum, dim3(g1), dim3(64), 0, sb, g, (const Fp*)g.ws.keyproj);
     } else  // one lane per key (per pair); params_mode: lanes [N, 2 N) allocate and prepare the generator (k_g1)
         hipLaunchKernelGGL(ck.g1, dim3(e->L.params_mode ? (unsigned)((2 * g.N + 63) / 64) : g1), dim3(64), 0, sb, g);
     hipEventRecord(b.ev_aux, sb);
-    if (e->opt.msg_mode && e->msg_len) hipLaunchKernelGGL(k_msg_input, dim3(g1), dim3(64), 0, sb, g);  // its inputs and the message segment
+    if (msg_input && e->msg_len) hipLaunchKernelGGL(k_msg_input, dim3(g1), dim3(64), 0, sb, g);  // its inputs and the message segment
+    if (e->L.n_keys) {  // blsw_engine_submit_aggregate_io: the head of instance_assignment (one, the keys' and the bitmap's inputs), one lane per element
+        bool any_inst = false;
+        for (uint32_t s = 0; s < steps; s++) any_inst = any_inst || b.h_desc[s].inst != nullptr;
+        const uint32_t n_elems = agg_instance_head(e->L);
+        for (uint32_t s0 = 0; any_inst && s0 < steps; s0 += 65535)  // grid.z = steps of the launch
+            hipLaunchKernelGGL(k_agg_instance, dim3((n_elems + 255) / 256, (unsigned)e->n, steps - s0 < 65535 ? steps - s0 : 65535), dim3(256), 0, sb, g, n_elems, s0);
+    }
     if (e->L.sig_mode) {
         // SignatureVar::new_variable(Input): no allocation chain (prepare(sig) wrote the instance variables)
     } else if (e->modes.g2_team)
@@ -565,6 +587,8 @@ static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint3
     if (o->pk_mode > 1 || o->sig_mode > 1 || ((o->pk_mode || o->sig_mode) && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
     // the message allocated as public inputs (UInt8::new_input_vec): the same circuits as pk_mode
     if (o->msg_mode > 1 || (o->msg_mode && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
+    // the aggregate circuit's own allocation modes (BLSW_AGG_*_INPUT): an aggregate engine only
+    if (o->agg_inputs > 15 || (o->agg_inputs && !o->n_keys)) return BLSW_ERR_ARG;
     return BLSW_OK;
 }
 
@@ -617,6 +641,7 @@ int blsw_engine_options_default(blsw_engine_options_t* o) {
     o->pk_mode = 0;
     o->sig_mode = 0;
     o->msg_mode = 0;
+    o->agg_inputs = 0;
     return BLSW_OK;
 }
 
@@ -625,7 +650,7 @@ int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_st
     if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
     blsw_layout_t L;
     const uint32_t K = options->n_pairs > 1 ? options->n_pairs : 1;
-    make_layout(msg_len, &L, options->n_keys, K, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1, options->msg_mode == 1);
+    options_layout(msg_len, options, &L);
     const bool staged = max_steps > 1 || n_buffers > 1;
     // the same workspace serves every kernel variant: the largest carve of the three mode combinations
     uint64_t need = 0;
@@ -692,8 +717,7 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     e->staged = max_steps > 1 || n_buffers > 1;
     e->cofactor_mode = options->cofactor_mode;
     e->chains_inlined = options->chain_variant == 2 || (options->chain_variant == 0 && !e->staged);
-    make_layout(msg_len, &e->L, options->n_keys, options->n_pairs > 1 ? options->n_pairs : 1, options->params_mode == 1, options->pk_mode == 1, options->sig_mode == 1,
-                options->msg_mode == 1);
+    options_layout(msg_len, options, &e->L);
     e->LS = e->L.n_pairs > 1 ? staging_layout_multi(e->L).LS : staging_layout(e->L, e->modes);
     for (int i = 0; i < BLSW_MAX_CONSUMED; i++) {
         e->consumed_ptr[i] = nullptr;
@@ -868,6 +892,14 @@ int blsw_engine_submit_aggregate(blsw_engine_t* e, const uint64_t* d_pks_xy, con
                                  uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream_) {
     if (!e || !e->L.n_keys || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
     StepDesc d = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, d_pks_xy, d_bitmap, d_count, nullptr};
+    return engine_submit(e, d, stream_);
+}
+
+// the same step with its instance_assignment (every aggregate engine; options.agg_inputs says which arguments are public inputs)
+int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                    uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream_) {
+    if (!e || !e->L.n_keys || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    StepDesc d = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, d_pks_xy, d_bitmap, d_count, nullptr, nullptr, d_instance};
     return engine_submit(e, d, stream_);
 }
 
@@ -1104,6 +1136,11 @@ int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg
 int blsw_layout_aggregate(uint32_t msg_len, uint32_t n_keys, blsw_layout_t* out) {
     if (!out || msg_len > 65535) return BLSW_ERR_ARG;
     make_layout(msg_len, out, n_keys);
+    return BLSW_OK;
+}
+int blsw_layout_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, blsw_layout_t* out) {
+    if (!out || msg_len > 65535 || n_keys == 0 || n_keys > 65535 || agg_inputs > 15) return BLSW_ERR_ARG;
+    make_layout_aggregate(msg_len, out, n_keys, agg_inputs);
     return BLSW_OK;
 }
 static uint64_t agg_workspace(uint64_t n, const blsw_layout_t& L, uint64_t* off_desc, uint64_t* off_keyproj, uint64_t* off_ws) {

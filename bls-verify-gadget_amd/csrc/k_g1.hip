@@ -1,6 +1,7 @@
 // libblsw.so, one translation unit per kernel family (see kcommon.hpp, build.py).
 // A chain unit: its compilations and the register policy of its grouped compilation are its entry in build.py's CHAIN_UNITS.
 #include "kcommon.hpp"
+#include "agg_input.hpp"
 
 namespace blsw {
 
@@ -69,17 +70,13 @@ struct KeyProjSrc {
         return {ld_fp(q), ld_fp(q + total), ld_fp(q + 2 * total)};
     }
 };
-// aggregate_verify: bitmap booleans, mapped_aggregate, then pk != 0 and prepare_g1 on the aggregated key
-__global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum)(Group g, const Fp* keyproj) {
-    if (g.chain_prio) __builtin_amdgcn_s_setprio(3);
-    uint64_t I = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= g.N) return;
-    LaneId id = lane_id(g, I);
-    const uint32_t nk = g.L.n_keys;
-    const uint8_t* bm = g.desc[id.s].bitmap + (uint64_t)id.i * nk;
+// aggregate_verify: bitmap booleans (Boolean::new_witness per key, constraints.rs:414-419; none when the bits are public inputs: the bitmap
+// segment is then empty, L.off_msg == L.off_bitmap), mapped_aggregate, then pk != 0 and prepare_g1 on the aggregated key
+template <class K>
+__device__ __forceinline__ void agg_sum_lane(const Group& g, const LaneId& id, uint64_t I, const K& src, const uint8_t* bm) {
+    const uint32_t nk = g.L.n_keys, n_bits = g.L.off_msg - g.L.off_bitmap;
     Emitter eb = EMIT(g, id, off_bitmap);
-    for (uint32_t k = 0; k < nk; k++) eb.put_bool(bm[k] != 0);  // Boolean::new_witness per key (constraints.rs:414-419)
-    KeyProjSrc src = {keyproj + I, g.N, g.N * nk};
+    for (uint32_t k = 0; k < n_bits; k++) eb.put_bool(bm[k] != 0);
     uint32_t count = 0;
     Proj<OpsFp> pk = chain_mapped_aggregate(EMIT(g, id, off_count), EMIT(g, id, off_agg), src, bm, nk, &count);
     G1ChainOut o = chain_g1_post(EMIT(g, id, off_pk_not_zero), EMIT(g, id, off_prep_pk), pk);
@@ -87,6 +84,28 @@ __global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum)(Group g,
     st_fp(g.ws.pkaff + g.N + I, o.ay);
     uint32_t* c = g.desc[id.s].count;
     if (c) c[id.i] = count;
+}
+__global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum)(Group g, const Fp* keyproj) {
+    if (g.chain_prio) __builtin_amdgcn_s_setprio(3);
+    uint64_t I = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= g.N) return;
+    LaneId id = lane_id(g, I);
+    const uint32_t nk = g.L.n_keys;
+    KeyProjSrc src = {keyproj + I, g.N, g.N * nk};
+    agg_sum_lane(g, id, I, src, g.desc[id.s].bitmap + (uint64_t)id.i * nk);
+}
+// the same with the keys as public inputs (L.pk_mode; agg_input.hpp): the affine keys of the step's inputs are the operands, k_agg_keys has not run
+struct LdFpGlobal {
+    __device__ __forceinline__ Fp operator()(const Fp* p) const { return ld_fp(p); }
+};
+__global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum_in)(Group g) {
+    if (g.chain_prio) __builtin_amdgcn_s_setprio(3);
+    uint64_t I = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= g.N) return;
+    LaneId id = lane_id(g, I);
+    const uint32_t nk = g.L.n_keys;
+    KeyInputSrc<LdFpGlobal> src = {reinterpret_cast<const Fp*>(g.desc[id.s].keys + (uint64_t)id.i * nk * 12), LdFpGlobal()};
+    agg_sum_lane(g, id, I, src, g.desc[id.s].bitmap + (uint64_t)id.i * nk);
 }
 
 }  // namespace blsw

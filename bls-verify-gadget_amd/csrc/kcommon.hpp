@@ -65,7 +65,8 @@ struct Workspace {
     Fp* coeff_h;     // [272][N]      line coefficients of prepare_g2(H(m))
     Fp* coeff_sig;   // [272][n_sig]  line coefficients of prepare_g2(sig)
     uint64_t n_sig;  // = N for the single-key circuit; = instances (not pairs) for the N+1-pair product
-    Fp* keyproj;     // [3][N * n_keys] allocated keys of the aggregate_verify circuit (projective), else nullptr
+    Fp* keyproj;     // [3][N * n_keys] allocated keys of the aggregate_verify circuit (projective); nullptr for the other circuits and when the
+                     // keys are public inputs (L.pk_mode: nothing allocates them, k_agg_sum_in reads the step's affine keys)
     Fp* staging;     // [N/64][rows_p][64] field witnesses (engine mode), or nullptr (direct mode): each wave of 64
                      // lanes owns one contiguous tile and appends 3 KiB rows to it (sequential HBM writes per wave)
     Fp* staging_inst;  // [n_sig/64][rows_i][64] the per-signature rows of the N+1-pair product staged the same way (sig allocation,
@@ -167,7 +168,7 @@ inline Workspace carve(void* base, uint64_t N, const blsw_layout_t& L, bool with
     w.coeff_h = reinterpret_cast<Fp*>(take(272ull * N * sizeof(Fp)));
     w.coeff_sig = reinterpret_cast<Fp*>(take(272ull * n_sig * sizeof(Fp)));
     w.n_sig = n_sig;
-    w.keyproj = L.n_keys ? reinterpret_cast<Fp*>(take(3ull * N * L.n_keys * sizeof(Fp))) : nullptr;
+    w.keyproj = L.n_keys && !L.pk_mode ? reinterpret_cast<Fp*>(take(3ull * N * L.n_keys * sizeof(Fp))) : nullptr;
     const bool small = N <= BLSW_LATENCY_MAX_LANES;  // (not a test of a carved pointer: with base == nullptr the carve only measures)
     w.cofv = small ? reinterpret_cast<Fp*>(take((uint64_t)BLSW_COFV_ELEMS * N * sizeof(Fp))) : nullptr;
     w.prepv_h = small ? reinterpret_cast<Fp*>(take((uint64_t)BLSW_PREPV_ELEMS * N * sizeof(Fp))) : nullptr;
@@ -383,6 +384,7 @@ BLSW_CHAIN_I(k_sha, (Group g, int want_bits, int write_u))
 BLSW_CHAIN_I(k_g1, (Group g))
 BLSW_CHAIN_I(k_agg_keys, (Group g, Fp* keyproj))
 BLSW_CHAIN_I(k_agg_sum, (Group g, const Fp* keyproj))
+BLSW_CHAIN_I(k_agg_sum_in, (Group g))
 BLSW_CHAIN_I(k_cofactor, (Group g))
 BLSW_CHAIN_I(k_cofactor_chunk, (Group g))
 BLSW_CHAIN_I(k_cofactor_join, (Group g))
@@ -403,6 +405,7 @@ __global__ void k_cofv_add_w(Group g);
 __global__ void k_cofv_join(Group g);
 __global__ void k_sha_values(Group g);
 __global__ void k_msg_input(Group g);
+__global__ void k_agg_instance(Group g, uint32_t n_elems, uint32_t s0);
 __global__ void k_map_values(Group g);
 __global__ void k_cofactor_values(Group g);
 __global__ void k_place_field(const Fp* __restrict__ staging, const Fp* __restrict__ pair, uint64_t first, uint32_t off_expand, uint32_t sha_bits,
@@ -479,6 +482,7 @@ struct ChainKernels {
     void (*g1)(Group);
     void (*agg_keys)(Group, Fp*);
     void (*agg_sum)(Group, const Fp*);
+    void (*agg_sum_in)(Group);  // the keys are public inputs (L.pk_mode): no allocated keys to read
     void (*cofactor)(Group);
     void (*cofactor_chunk)(Group);  // the cofactor segment with its three chunks on three lanes, and the join (cofactor_par.hpp)
     void (*cofactor_join)(Group);
@@ -498,8 +502,8 @@ inline ChainKernels chain_kernels(bool inlined, bool quad) {
 #define BLSW_PICK_I(name) (inlined ? name##_inl : name)
 #define BLSW_PICK_Q(name) (quad ? name##_q : name)
 #define BLSW_PICK_IQ(name) (quad ? name##_q : BLSW_PICK_I(name))
-    return {BLSW_PICK_I(k_sha), BLSW_PICK_I(k_g1), BLSW_PICK_I(k_agg_keys), BLSW_PICK_I(k_agg_sum), BLSW_PICK_I(k_cofactor), BLSW_PICK_I(k_cofactor_chunk),
-            BLSW_PICK_I(k_cofactor_join), BLSW_PICK_IQ(k_g2_alloc), BLSW_PICK_IQ(k_map), BLSW_PICK_IQ(k_prepare), BLSW_PICK_Q(k_prepv_chain),
+    return {BLSW_PICK_I(k_sha), BLSW_PICK_I(k_g1), BLSW_PICK_I(k_agg_keys), BLSW_PICK_I(k_agg_sum), BLSW_PICK_I(k_agg_sum_in), BLSW_PICK_I(k_cofactor),
+            BLSW_PICK_I(k_cofactor_chunk), BLSW_PICK_I(k_cofactor_join), BLSW_PICK_IQ(k_g2_alloc), BLSW_PICK_IQ(k_map), BLSW_PICK_IQ(k_prepare), BLSW_PICK_Q(k_prepv_chain),
             BLSW_PICK_Q(k_cofv_chain), BLSW_PICK_Q(k_cofv_bwd), BLSW_PICK_Q(k_cofv_acc), BLSW_PICK_Q(k_cofv_az), quad ? 4u : 1u};
 #undef BLSW_PICK_I
 #undef BLSW_PICK_Q

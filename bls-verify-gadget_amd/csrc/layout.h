@@ -39,8 +39,11 @@ inline uint32_t seg_miller(uint32_t n_pairs) { return 62 * 36 + 68 * 30 - 30 + 6
 // msg_input: UInt8::new_input_vec (ark-r1cs-std 0.4.0), single-key circuit with Constant parameters only: the message is packed into
 // msg_input_chunks(msg_len) public inputs of MSG_CHUNK_BYTES bytes each, allocated before the key's and the signature's, and the message segment
 // holds each chunk's AllocatedFp::to_bits_le (SEG_MSG_CHUNK witnesses per chunk) instead of 8 booleans per byte.
+// aggregate_verify (n_keys > 0) takes the same three flags for its keys (every key Input: 3 n_keys instance variables, an empty keys segment), its
+// message and its signature, and bitmap_input for Boolean::new_input per bit (n_keys instance variables, an empty bitmap segment; the booleanity
+// constraints stay). Allocation order keys, bitmap, message, signature (constraints.rs:394-441) is the order of the instance variables.
 inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0, uint32_t n_pairs = 1, bool params_witness = false, bool pk_input = false,
-                        bool sig_input = false, bool msg_input = false) {
+                        bool sig_input = false, bool msg_input = false, bool bitmap_input = false) {
     std::vector<uint8_t> msg(msg_len ? msg_len : 1, 0);
     BitSink s;
     s.init(nullptr, 0);
@@ -48,7 +51,7 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
     expand_message_w(s, msg.data(), msg_len, false, uw);
     L->msg_len = msg_len;
     const uint32_t msg_chunks = msg_input ? msg_input_chunks(msg_len) : 0;
-    L->n_instance_vars = 1 + msg_chunks + (pk_input ? 3 : 0) + (sig_input ? 6 : 0);
+    L->n_instance_vars = 1 + msg_chunks + (pk_input ? 3 * (n_keys ? n_keys : 1) : 0) + (n_keys && bitmap_input ? n_keys : 0) + (sig_input ? 6 : 0);
     L->pk_mode = pk_input ? 1 : 0;
     L->sig_mode = sig_input ? 1 : 0;
     L->sha_bits = (uint32_t)s.nbits;
@@ -57,9 +60,9 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
     L->off_keys = L->off_bitmap = L->off_count = L->off_agg = 0;
     if (n_keys) {  // keys, bitmap booleans, msg, sig, count, per-key (select 3 + add 12 (not the first) + addmany 33)
         L->off_keys = o;
-        o += n_keys * SEG_PK_ALLOC;
+        o += pk_input ? 0 : n_keys * SEG_PK_ALLOC;
         L->off_bitmap = o;
-        o += n_keys;
+        o += bitmap_input ? 0 : n_keys;
     }
     const uint32_t K = n_keys ? 1 : (n_pairs ? n_pairs : 1);
     L->n_pairs = K;
@@ -114,5 +117,14 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
     o += SEG_IS_ONE;
     L->n_witness = o;
 }
+// aggregate_verify with its mask of Input arguments (BLSW_AGG_*_INPUT, include/blsw.h)
+inline void make_layout_aggregate(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys, uint32_t agg_inputs) {
+    make_layout(msg_len, L, n_keys, 1, false, (agg_inputs & BLSW_AGG_KEYS_INPUT) != 0, (agg_inputs & BLSW_AGG_SIG_INPUT) != 0, (agg_inputs & BLSW_AGG_MSG_INPUT) != 0,
+                (agg_inputs & BLSW_AGG_BITMAP_INPUT) != 0);
+}
+// the instance variables of an aggregate_verify layout: [1 | 3 per key | 1 per bitmap bit | message chunks | 6 of the signature], the selected groups only
+BLSW_HD uint32_t agg_bitmap_is_input(const blsw_layout_t& L) { return L.n_keys && L.off_msg == L.off_bitmap; }
+BLSW_HD uint32_t agg_inst_bitmap_base(const blsw_layout_t& L) { return 1 + (L.pk_mode ? 3 * L.n_keys : 0); }
+BLSW_HD uint32_t agg_inst_msg_base(const blsw_layout_t& L) { return agg_inst_bitmap_base(L) + (agg_bitmap_is_input(L) ? L.n_keys : 0); }
 
 }  // namespace blsw

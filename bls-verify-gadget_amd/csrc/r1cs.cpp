@@ -111,6 +111,11 @@ static B b_alloc() {  // AllocatedBool::new_witness: (1 - b) * b = 0
     S->enforce(lc_sub(lc_const(fp_one()), lc_var(x)), lc_var(x), Lc());
     return {1, false, x};
 }
+static B b_alloc_input() {  // AllocatedBool::new_variable(.., Input): an instance variable, the same booleanity constraint, no witness
+    uint32_t x = S->alloc_input();
+    S->enforce(lc_sub(lc_const(fp_one()), lc_var(x)), lc_var(x), Lc());
+    return {1, false, x};
+}
 static B b_not(const B& a) {
     if (a.kind == 0) return b_const(!a.cv);
     return {(uint8_t)(a.kind == 1 ? 2 : 1), false, a.var};
@@ -1250,14 +1255,14 @@ static B verify_gadget(const std::vector<Pt<T1>>& pks, const std::vector<std::ve
     return v12_is_eq(fe, v12_one());
 }
 static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool params_witness, bool pk_input = false, bool sig_input = false,
-                    bool msg_input = false) {
-    if (n_keys) {  // constraints.rs:378-441: keys, bitmap booleans, msg, params, sig, aggregate_verify
+                    bool msg_input = false, bool bitmap_input = false) {
+    if (n_keys) {  // constraints.rs:378-441: keys, bitmap booleans, msg, params, sig, aggregate_verify; each of the four Witness or Input (BLSW_AGG_*_INPUT)
         std::vector<Pt<T1>> keys;
-        for (uint32_t k = 0; k < n_keys; k++) keys.push_back(g1_new_witness());
+        for (uint32_t k = 0; k < n_keys; k++) keys.push_back(pk_input ? pt_input<T1>() : g1_new_witness());
         std::vector<B> bitmap;
-        for (uint32_t k = 0; k < n_keys; k++) bitmap.push_back(b_alloc());
-        std::vector<U8> msg = msg_alloc(msg_len);
-        Pt<T2> sig = g2_new_witness();
+        for (uint32_t k = 0; k < n_keys; k++) bitmap.push_back(bitmap_input ? b_alloc_input() : b_alloc());
+        std::vector<U8> msg = msg_input ? msg_alloc_input(msg_len) : msg_alloc(msg_len);
+        Pt<T2> sig = sig_input ? pt_input<T2>() : g2_new_witness();
         // mapped_aggregate (constraints.rs:169-191)
         U32 count;
         for (int i = 0; i < 32; i++) count.b[i] = b_alloc();
@@ -1282,14 +1287,19 @@ static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool pa
     (void)verify_gadget(pks, msgs, sig, params_witness ? &g1 : nullptr);
 }
 
-// io_modes: bit 0 = pk Input, bit 1 = sig Input, bit 2 = msg Input (single-key circuit with Constant parameters)
+// io_modes: bit 0 = pk Input, bit 1 = sig Input, bit 2 = msg Input (single-key circuit with Constant parameters); bit 3 = bitmap Input: the
+// aggregate circuit, whose keys, signature and message take bits 0-2 (the callers translate BLSW_AGG_*_INPUT; io_modes >= 16 marks an aggregate
+// circuit reached through blsw_matrices_*_aggregate_inputs: n_keys with io_modes through the other entry points stays refused)
+enum : uint32_t { IO_PK = 1, IO_SIG = 2, IO_MSG = 4, IO_BITMAP = 8, IO_AGG = 16 };
 static int run(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, Sys& sys, uint32_t params_mode = 0, uint32_t io_modes = 0) {
     if (msg_len > 65535 || n_keys > 65535 || (n_keys && n_pairs > 1) || n_pairs == 0 || n_pairs > 4096) return BLSW_ERR_ARG;
     if (params_mode > 1 || (params_mode && (n_keys || n_pairs != 1))) return BLSW_ERR_ARG;
-    if (io_modes > 7 || (io_modes && (n_keys || n_pairs != 1 || params_mode))) return BLSW_ERR_ARG;
+    const bool agg = (io_modes & IO_AGG) != 0;
+    if (io_modes > 31 || (agg && !n_keys) || (!agg && (io_modes > 7 || (io_modes && (n_keys || n_pairs != 1 || params_mode))))) return BLSW_ERR_ARG;
     S = &sys;
-    sys.n_inst = 1 + ((io_modes & 4) ? msg_input_chunks(msg_len) : 0) + ((io_modes & 1) ? 3 : 0) + ((io_modes & 2) ? 6 : 0);
-    circuit(msg_len, n_keys, n_pairs, params_mode == 1, (io_modes & 1) != 0, (io_modes & 2) != 0, (io_modes & 4) != 0);
+    sys.n_inst = 1 + ((io_modes & IO_MSG) ? msg_input_chunks(msg_len) : 0) + ((io_modes & IO_PK) ? 3 * (n_keys ? n_keys : 1) : 0) + ((io_modes & IO_SIG) ? 6 : 0) +
+                 ((io_modes & IO_BITMAP) ? n_keys : 0);
+    circuit(msg_len, n_keys, n_pairs, params_mode == 1, (io_modes & IO_PK) != 0, (io_modes & IO_SIG) != 0, (io_modes & IO_MSG) != 0, (io_modes & IO_BITMAP) != 0);
     sys.finish();
     S = nullptr;
     return BLSW_OK;
@@ -1396,5 +1406,20 @@ int blsw_matrices_info_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_m
 int blsw_matrices_fill_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
     if (msg_mode > 1 || pk_mode > 1 || sig_mode > 1) return BLSW_ERR_ARG;
     return matrices_fill(msg_len, 0, 1, 0, info, out, pk_mode | sig_mode << 1 | msg_mode << 2);
+}
+// BLSW_AGG_*_INPUT -> io_modes of run(); mask 0 is the circuit of blsw_matrices_info(msg_len, n_keys, 1)
+static uint32_t agg_io_modes(uint32_t m) {
+    using namespace blsw::r1cs;
+    if (!m) return 0;
+    return IO_AGG | ((m & BLSW_AGG_KEYS_INPUT) ? IO_PK : 0) | ((m & BLSW_AGG_BITMAP_INPUT) ? IO_BITMAP : 0) | ((m & BLSW_AGG_MSG_INPUT) ? IO_MSG : 0) |
+           ((m & BLSW_AGG_SIG_INPUT) ? IO_SIG : 0);
+}
+int blsw_matrices_info_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, blsw_matrices_info_t* out) {
+    if (agg_inputs > 15 || n_keys == 0) return BLSW_ERR_ARG;
+    return matrices_info(msg_len, n_keys, 1, 0, out, agg_io_modes(agg_inputs));
+}
+int blsw_matrices_fill_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
+    if (agg_inputs > 15 || n_keys == 0) return BLSW_ERR_ARG;
+    return matrices_fill(msg_len, n_keys, 1, 0, info, out, agg_io_modes(agg_inputs));
 }
 }

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 12
+#define BLSW_ABI_VERSION 13
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -69,7 +69,11 @@ typedef struct {
      * 0 = one, 1 .. n_instance_vars - 1 = the inputs, n_instance_vars + k = witness k.
      * The message allocated with UInt8::new_input_vec (blsw_layout_inputs, msg_mode 1) has no field of its own here: it comes first, as
      * c = ceil(msg_len / 47) public inputs, and the caller recovers c as n_instance_vars - 1 - 3 * pk_mode - 6 * sig_mode. Its segment is then
-     * stride_msg = 761 * c witnesses instead of 8 * msg_len. */
+     * stride_msg = 761 * c witnesses instead of 8 * msg_len.
+     * aggregate_verify with Input arguments (blsw_layout_aggregate_inputs, ABI 13) has no field of its own either: pk_mode / sig_mode report the keys' /
+     * the signature's mode, the message's mode shows in stride_msg (761 * c instead of 8 * msg_len) and the bitmap's in off_msg == off_bitmap (its segment
+     * is empty); off_bitmap == off_keys says the same of the keys. instance_assignment = [1, key_0.x, key_0.y, key_0.z, .., key_{K-1}.z, b_0 .. b_{K-1},
+     * m_0 .. m_{c-1}, sig.x.c0 .. sig.z.c1], the selected groups only. */
     uint32_t pk_mode, sig_mode;
 } blsw_layout_t;
 
@@ -79,6 +83,19 @@ int blsw_layout(uint32_t msg_len, blsw_layout_t* out);
 /* layout of the aggregate_verify circuit with n_keys public keys (keys Witness, bitmap booleans Witness, msg, sig, then
  * mapped_aggregate + verify: src/constraints.rs:153-191, 378-441). n_keys == 0 gives blsw_layout. Host only. */
 int blsw_layout_aggregate(uint32_t msg_len, uint32_t n_keys, blsw_layout_t* out);
+/* ABI 13: aggregate_verify with each of its four arguments Witness (0, the reference's test) or Input, independently: agg_inputs is a mask of */
+#define BLSW_AGG_KEYS_INPUT   1   /* every PublicKeyVar::new_variable(.., Input)            */
+#define BLSW_AGG_BITMAP_INPUT 2   /* every Boolean::new_input                               */
+#define BLSW_AGG_MSG_INPUT    4   /* UInt8::new_input_vec, as options.msg_mode 1            */
+#define BLSW_AGG_SIG_INPUT    8   /* SignatureVar::new_variable(.., Input)                  */
+/* Allocation order is the reference test's (constraints.rs:394-441: keys, bitmap, message, parameters Constant, signature), hence the order of the
+ * instance variables (blsw_layout_t.pk_mode). An Input key is the pk_mode rule K times: x, y, z instance variables ((0, 1, 0) for the (0, 0) input), no
+ * witnesses, no prime-order check; the keys segment is empty. An Input bitmap bit (AllocatedBool::new_variable with Input) is an instance variable that
+ * keeps its booleanity constraint (1 - b) * b = 0: no witness, the bitmap segment is empty; select, the additions and addmany of mapped_aggregate
+ * allocate what they allocate for witnesses, and count stays a witness (constraints.rs:179). Message and signature as blsw_layout_inputs; the
+ * signature's six inputs are the last six, the message chunks sit in front of them. agg_inputs 0 = blsw_layout_aggregate field for field.
+ * BLSW_ERR_ARG: agg_inputs > 15, n_keys == 0. Host only. */
+int blsw_layout_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, blsw_layout_t* out);
 int blsw_aggregate_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_keys, uint64_t* bytes);
 /* BlsSignatureVerifyGadget::aggregate_verify for n independent instances of n_keys keys each (same message per instance):
  *   d_pks_xy [n][n_keys][12] u64, d_bitmap [n][n_keys] bytes (0/1: Boolean::new_witness), d_sig_xy [n][24], d_msg [n][msg_len]
@@ -192,6 +209,10 @@ typedef struct {
     uint32_t msg_mode;     /* message allocation (src/constraints.rs:341, ABI 12): 0 (default) UInt8::new_witness_vec, 1 UInt8::new_input_vec (blsw_layout_inputs):
                               blsw_engine_submit_io writes the message chunks into instance_assignment as well. Single-key circuit with Constant parameters
                               and g2_mode 0 only, as pk_mode. */
+    uint32_t agg_inputs;   /* aggregate_verify engines (n_keys > 0, ABI 13): mask of BLSW_AGG_*_INPUT (blsw_layout_aggregate_inputs), 0 (default) = every argument
+                              Witness. With BLSW_AGG_KEYS_INPUT nothing allocates keys: no allocation kernel runs and the workspace holds no projective keys.
+                              blsw_engine_submit_aggregate_io also writes instance_assignment. The aggregate circuit's modes are this mask: pk_mode, sig_mode
+                              and msg_mode stay refused together with n_keys. BLSW_ERR_ARG: a value above 15, a non-zero value with n_keys == 0. */
 } blsw_engine_options_t;
 /* the defaults (pure: measurement scripts set the fields they want to vary). The one environment variable the library reads is the
  * diagnostic BLSW_TRACE_GROUP=1: an engine prints its launch groups' stage times to stderr at blsw_engine_destroy. */
@@ -249,6 +270,13 @@ int blsw_engine_submit_bytes(blsw_engine_t* e, const uint8_t* d_pk48, const uint
  *   d_witness [n][witness_stride] (stride >= blsw_layout_aggregate().n_witness; may be NULL), d_result [n] int32, d_count [n] uint32 (may be NULL) */
 int blsw_engine_submit_aggregate(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
                                  uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream);
+/* blsw_engine_submit_aggregate for an engine with options.agg_inputs (it works for every aggregate engine, mask 0 included: then it writes [1]):
+ * additionally writes d_instance [n][n_instance_vars][6] u64 = each instance's instance_assignment (element 0 = one; Montgomery limbs, or canonical
+ * integers with options.output_form 1); d_instance may be NULL. blsw_engine_submit_aggregate and blsw_engine_submit_aggregate_compact work on an engine
+ * with a non-zero mask and write no instance vector (the compact form carries witnesses only). BLSW_ERR_ARG on a single-key engine.
+ * The direct call blsw_aggregate_verify_batch has no options and stays all-Witness; a direct-mode engine is the direct path of these shapes. */
+int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                    uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream);
 /* The N+1-pair product (blsw_verify_multi_batch's circuit) through the engine, for an engine created with options.n_pairs = K: one
  * batch of n instances, same grouping / staging / streaming placement / consumer mode as blsw_engine_submit — more instances are in
  * flight than output tensors exist (a vector is 4.19 GB at K = 128), which the direct call cannot do.
@@ -345,6 +373,10 @@ int blsw_matrices_fill_io(uint32_t msg_len, uint32_t pk_mode, uint32_t sig_mode,
 /* the same for the circuit of blsw_layout_inputs (ABI 12); msg_mode 0 = the two calls above */
 int blsw_matrices_info_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, blsw_matrices_info_t* out);
 int blsw_matrices_fill_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, uint32_t sig_mode, const blsw_matrices_info_t* info, blsw_matrices_t* out);
+/* the same for the circuit of blsw_layout_aggregate_inputs (ABI 13): columns as everywhere (one, the inputs in allocation order, the witnesses);
+ * agg_inputs 0 = blsw_matrices_info / _fill (msg_len, n_keys, 1) */
+int blsw_matrices_info_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, blsw_matrices_info_t* out);
+int blsw_matrices_fill_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out);
 
 /* Device R1CS evaluator (ABI 11): checks and evaluates the matrices above against witness vectors on the GPU — arkworks'
  * cs.is_satisfied() / cs.which_is_unsatisfied() and the A z, B z, C z a prover computes first, for n instances at a time.

@@ -167,7 +167,8 @@ class ConstraintSystem {
         return w;
     }
     // instance_assignment of system i after verify: n_instance_vars elements (element 0 = one; then the message chunks of UInt8::new_input_vec and
-    // the coordinates of the points allocated with AllocationMode::Input, in allocation order), same element encoding as witness_assignment
+    // the coordinates of the points allocated with AllocationMode::Input, in allocation order), same element encoding as witness_assignment.
+    // After aggregate_verify with Input arguments: [1, the keys' x, y, z, the bitmap bits, the message chunks, the signature's six], the Input groups only
     std::vector<uint64_t> instance_assignment(size_t i) const {
         if (i >= n_) throw Error("instance_assignment out of range", BLSW_ERR_ARG);
         std::vector<uint64_t> v((size_t)layout_.n_instance_vars * 6);
@@ -199,7 +200,8 @@ class ConstraintSystem {
     detail::DeviceBytes r1cs_buffer_;
     blsw_matrices_info_t matrices_info() const {
         blsw_matrices_info_t info;
-        check(msg_mode_                          ? blsw_matrices_info_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info)
+        check(layout_.n_keys && agg_inputs_      ? blsw_matrices_info_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info)
+              : msg_mode_                        ? blsw_matrices_info_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info)
               : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
               : layout_.params_mode              ? blsw_matrices_info_params(msg_len_, layout_.params_mode, &info)
                                                  : blsw_matrices_info(msg_len_, layout_.n_keys, 1, &info),
@@ -219,7 +221,8 @@ class ConstraintSystem {
             m.col[k] = col[k].data();
             m.val[k] = val[k].data();
         }
-        check(msg_mode_                          ? blsw_matrices_fill_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info, &m)
+        check(layout_.n_keys && agg_inputs_      ? blsw_matrices_fill_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info, &m)
+              : msg_mode_                        ? blsw_matrices_fill_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info, &m)
               : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_fill_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info, &m)
               : layout_.params_mode              ? blsw_matrices_fill_params(msg_len_, layout_.params_mode, &info, &m)
                                                  : blsw_matrices_fill(msg_len_, layout_.n_keys, 1, &info, &m),
@@ -240,6 +243,7 @@ class ConstraintSystem {
         msg_mode_ = msg_mode;
     }
     uint32_t msg_mode_ = 0;  // the message allocated with UInt8::new_input_vec (its chunks are instance_assignment[1 .. c])
+    uint32_t agg_inputs_ = 0;  // aggregate_verify: BLSW_AGG_*_INPUT of the circuit it synthesised (blsw_layout_aggregate_inputs)
     std::vector<int32_t> status_;
 };
 
@@ -309,12 +313,14 @@ class PublicKeyVar {
         cs.set_io(mode == AllocationMode::Input ? 1u : 0u, cs.layout_.sig_mode, cs.msg_mode_);
         PublicKeyVar v;
         v.keys_ = keys;
+        v.input_ = mode == AllocationMode::Input;
         return v;
     }
 
    private:
     friend struct BlsSignatureVerifyGadget;
     std::vector<PublicKey> keys_;
+    bool input_ = false;
 };
 class SignatureVar {
    public:
@@ -324,15 +330,18 @@ class SignatureVar {
         cs.set_io(cs.layout_.pk_mode, mode == AllocationMode::Input ? 1u : 0u, cs.msg_mode_);
         SignatureVar v;
         v.sigs_ = sigs;
+        v.input_ = mode == AllocationMode::Input;
         return v;
     }
 
    private:
     friend struct BlsSignatureVerifyGadget;
     std::vector<Signature> sigs_;
+    bool input_ = false;
 };
 
-// Boolean<ConstraintF>: one Boolean of every system — the gadget's output, or a bitmap entry allocated with new_witness (constraints.rs:414-419)
+// Boolean<ConstraintF>: one Boolean of every system — the gadget's output, or a bitmap entry allocated with new_witness (constraints.rs:414-419) or
+// new_input (AllocatedBool::new_variable with Input: a public input that keeps its booleanity constraint and has no witness)
 class Boolean {
    public:
     const std::vector<bool>& value() const { return v_; }
@@ -342,10 +351,16 @@ class Boolean {
         b.v_ = values;
         return b;
     }
+    static Boolean new_input(ConstraintSystem& cs, const std::vector<bool>& values) {
+        Boolean b = new_witness(cs, values);
+        b.input_ = true;
+        return b;
+    }
 
    private:
     friend struct BlsSignatureVerifyGadget;
     std::vector<bool> v_;
+    bool input_ = false;
 };
 // UInt32<ConstraintF>: the effective public key count of aggregate_verify (constraints.rs:177-189)
 class UInt32 {
@@ -436,6 +451,9 @@ struct BlsSignatureVerifyGadget {
     // as in verify. The infinity encoding of a KEY decodes (PublicKey::try_from accepts it, and a key whose bitmap bit is 0 never enters
     // the aggregate, constraints.rs:169-191): such a system returns the gadget's own Boolean. Synchronous; direct-mode batch entry
     // blsw_aggregate_verify_batch.
+    // Each argument may be allocated as Input instead (PublicKeyVar / SignatureVar::new_variable(.., Input), Boolean::new_input,
+    // UInt8::new_input_vec; all keys in one mode, all bits in one mode): the circuit is then the one of blsw_layout_aggregate_inputs, run by a
+    // direct-mode engine with options.agg_inputs, and instance_assignment(i) holds the public inputs.
     static std::pair<Boolean, UInt32> aggregate_verify(const ParametersVar& parameters, const std::vector<PublicKeyVar>& public_keys, const std::vector<Boolean>& bitmap,
                                                        const MessageVar& message, const SignatureVar& signature) {
         if (!parameters.cs_) throw Error("aggregate_verify: parameters were not allocated in a ConstraintSystem", BLSW_ERR_ARG);
@@ -444,7 +462,15 @@ struct BlsSignatureVerifyGadget {
         if (K == 0 || bitmap.size() != K) throw Error("aggregate_verify: public_keys.len() == bitmap.len() > 0", BLSW_ERR_ARG);  // constraints.rs:160
         if (cs.layout_.params_mode || cs.engine_) throw Error("aggregate_verify: Constant parameters, a ConstraintSystem not used by verify", BLSW_ERR_ARG);
         if (signature.sigs_.size() != n || message.bytes().size() != n * cs.msg_len_) throw Error("aggregate_verify: variables of another ConstraintSystem", BLSW_ERR_ARG);
-        check(blsw_layout_aggregate(cs.msg_len_, (uint32_t)K, &cs.layout_), "blsw_layout_aggregate");
+        for (size_t k = 1; k < K; k++)
+            if (public_keys[k].input_ != public_keys[0].input_ || bitmap[k].input_ != bitmap[0].input_)
+                throw Error("aggregate_verify: every key in one AllocationMode, every bitmap bit in one AllocationMode", BLSW_ERR_ARG);
+        const uint32_t mask = (public_keys[0].input_ ? BLSW_AGG_KEYS_INPUT : 0u) | (bitmap[0].input_ ? BLSW_AGG_BITMAP_INPUT : 0u) |
+                              (message.is_input() ? BLSW_AGG_MSG_INPUT : 0u) | (signature.input_ ? BLSW_AGG_SIG_INPUT : 0u);
+        cs.agg_inputs_ = mask;
+        cs.msg_mode_ = 0;  // the aggregate circuit's modes are the mask
+        check(mask ? blsw_layout_aggregate_inputs(cs.msg_len_, (uint32_t)K, mask, &cs.layout_) : blsw_layout_aggregate(cs.msg_len_, (uint32_t)K, &cs.layout_),
+              "blsw_layout_aggregate");
         if (cs.device_ >= 0) hip_check(hipSetDevice(cs.device_), "hipSetDevice");
         // compressed inputs, system-major: keys [n][K][48], bitmap [n][K], signatures [n][96]
         std::vector<uint8_t> pk(n * K * 48), bm(n * K), sg(n * 96);
@@ -480,16 +506,35 @@ struct BlsSignatureVerifyGadget {
         d_bm.upload(bm.data(), bm.size());
         if (!message.bytes().empty()) d_msg.upload(message.bytes().data(), message.bytes().size());
         uint64_t bytes = 0;
-        check(blsw_aggregate_workspace_bytes(n, cs.msg_len_, (uint32_t)K, &bytes), "blsw_aggregate_workspace_bytes");
-        cs.workspace_ = detail::DeviceBytes(bytes);
+        detail::DeviceBytes d_count(n * 4);
         cs.witness_ = detail::DeviceBytes(n * (size_t)cs.layout_.n_witness * 48);
         cs.result_ = detail::DeviceBytes(n * 4);
-        detail::DeviceBytes d_count(n * 4);
+        if (mask) {  // a direct-mode engine of the circuit with these Input arguments; the step also writes instance_assignment
+            blsw_engine_options_t opt;
+            check(blsw_engine_options_default(&opt), "blsw_engine_options_default");
+            opt.device = cs.device_;
+            opt.n_keys = (uint32_t)K;
+            opt.agg_inputs = mask;
+            check(blsw_engine_workspace_bytes_ex(n, cs.msg_len_, 1, 1, &opt, &bytes), "blsw_engine_workspace_bytes_ex");
+            cs.workspace_ = detail::DeviceBytes(bytes);
+            cs.instance_ = detail::DeviceBytes(n * (size_t)cs.layout_.n_instance_vars * 48);
+            cs.pk_xy_ = std::move(d_pk_xy);  // the step's inputs stay alive with the system
+            check(blsw_engine_create_ex(&cs.engine_, n, cs.msg_len_, 1, 1, &opt, cs.workspace_.get(), bytes), "blsw_engine_create_ex");
+            check(blsw_engine_submit_aggregate_io(cs.engine_, static_cast<const uint64_t*>(cs.pk_xy_.get()), static_cast<const uint8_t*>(d_bm.get()),
+                                                  static_cast<const uint64_t*>(cs.sig_xy_.get()), static_cast<const uint8_t*>(d_msg.get()),
+                                                  static_cast<uint64_t*>(cs.instance_.get()), static_cast<uint64_t*>(cs.witness_.get()), cs.layout_.n_witness,
+                                                  static_cast<int32_t*>(cs.result_.get()), static_cast<uint32_t*>(d_count.get()), nullptr),
+                  "blsw_engine_submit_aggregate_io");
+            check(blsw_engine_flush(cs.engine_, nullptr), "blsw_engine_flush");
+        } else {
+        check(blsw_aggregate_workspace_bytes(n, cs.msg_len_, (uint32_t)K, &bytes), "blsw_aggregate_workspace_bytes");
+        cs.workspace_ = detail::DeviceBytes(bytes);
         check(blsw_aggregate_verify_batch(static_cast<const uint64_t*>(d_pk_xy.get()), static_cast<const uint8_t*>(d_bm.get()), (uint32_t)K,
                                           static_cast<const uint64_t*>(cs.sig_xy_.get()), static_cast<const uint8_t*>(d_msg.get()), cs.msg_len_, n,
                                           static_cast<uint64_t*>(cs.witness_.get()), cs.layout_.n_witness, static_cast<int32_t*>(cs.result_.get()),
                                           static_cast<uint32_t*>(d_count.get()), cs.workspace_.get(), bytes, nullptr),
               "blsw_aggregate_verify_batch");
+        }
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n);
         cs.result_.download(r.data(), n * 4);
