@@ -40,6 +40,14 @@ class blsw_matrices_t(ctypes.Structure):
     _fields_ = [("row_ptr", ctypes.POINTER(ctypes.c_uint64) * 3), ("col", ctypes.POINTER(ctypes.c_uint32) * 3), ("val", ctypes.POINTER(ctypes.c_uint64) * 3)]
 
 
+class blsw_compact_layout_t(ctypes.Structure):
+    """where the witnesses of a step live in its compact buffer (include/blsw.h, ABI 14)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in "n off_staging off_pair total".split()] + \
+               [(n, ctypes.c_uint32) for n in "n_witness off_expand sha_bits sha_words split_row staging_rows pair_rows moved_lo moved_len moved_at".split()]
+
+
+COMPACT_BIT, COMPACT_TILE, COMPACT_PAIR = 0, 1, 2  # regions of compact_locate
+
 ERR_BUSY = 6
 
 
@@ -133,6 +141,11 @@ def lib():
         L.blsw_r1cs_destroy.argtypes = [vp]
         L.blsw_r1cs_check.argtypes = [vp, vp, u64, vp, u64, u64, u32, vp, vp, vp]
         L.blsw_r1cs_evaluate.argtypes = [vp, vp, u64, vp, u64, u64, u32, u64, u64, vp, vp, vp, vp]
+        cl = ctypes.POINTER(blsw_compact_layout_t)
+        L.blsw_compact_layout.argtypes = [u64, u32, ctypes.POINTER(blsw_engine_options_t), cl]
+        L.blsw_compact_locate.argtypes = [cl, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.blsw_r1cs_check_compact.argtypes = [vp, cl, vp, vp, u64, vp, vp, vp]
+        L.blsw_r1cs_evaluate_compact.argtypes = [vp, cl, vp, vp, u64, u64, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -145,7 +158,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch",
                     "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate", "blsw_layout_inputs",
                     "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs", "blsw_layout_aggregate_inputs", "blsw_matrices_info_aggregate_inputs",
-                    "blsw_matrices_fill_aggregate_inputs", "blsw_engine_submit_aggregate_io"]
+                    "blsw_matrices_fill_aggregate_inputs", "blsw_engine_submit_aggregate_io", "blsw_compact_layout", "blsw_compact_locate",
+                    "blsw_r1cs_check_compact", "blsw_r1cs_evaluate_compact"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -245,6 +259,41 @@ def engine_options(**overrides):
     return o
 
 
+def compact_layout(n, msg_len=32, **options):
+    """blsw_compact_layout: where every witness element of a compact step of n instances lives (blsw_compact_layout_t), for the engine options given
+    as in WitnessEngine(...). Host only."""
+    opt = options.pop("_opt", None) or engine_options(**options)
+    c = blsw_compact_layout_t()
+    rc = lib().blsw_compact_layout(n, msg_len, ctypes.byref(opt), ctypes.byref(c))
+    if rc:
+        raise BlswError("blsw_compact_layout failed: %d" % rc)
+    return c
+
+
+def compact_locate(layout, k, lane):
+    """blsw_compact_locate -> (region COMPACT_BIT / _TILE / _PAIR, byte offset in the buffer, bit position in the u32 word at that offset)"""
+    region, off, bit = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    rc = lib().blsw_compact_locate(ctypes.byref(layout), k, lane, ctypes.byref(region), ctypes.byref(off), ctypes.byref(bit))
+    if rc:
+        raise BlswError("blsw_compact_locate failed: %d" % rc)
+    return region.value, off.value, bit.value
+
+
+def compact_locate_all(layout, lane):
+    """compact_locate of every witness index for one lane -> (region uint8 [n_witness], byte offset int64 [n_witness], bit uint8 [n_witness])"""
+    import numpy as np
+
+    nw = layout.n_witness
+    region, off, bit = np.zeros(nw, np.uint8), np.zeros(nw, np.int64), np.zeros(nw, np.uint8)
+    r, o, b = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    fn, lp, rp, op, bp = lib().blsw_compact_locate, ctypes.byref(layout), ctypes.byref(r), ctypes.byref(o), ctypes.byref(b)
+    for k in range(nw):
+        if fn(lp, k, lane, rp, op, bp):
+            raise BlswError("blsw_compact_locate failed at k = %d" % k)
+        region[k], off[k], bit[k] = r.value, o.value, b.value
+    return region, off, bit
+
+
 class WitnessEngine:
     """Thin wrapper of blsw_engine_*: submit batches, flush, read results. max_steps batches are fused per launch group.
     Streaming consumers use the step numbers returned by submit(): wait_step(seq) / output_consumed(tensor)."""
@@ -260,6 +309,7 @@ class WitnessEngine:
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         opt = engine_options(**options)
         opt.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._opt = opt
         self.n_keys = int(opt.n_keys)
         self.n_pairs = int(opt.n_pairs) if opt.n_pairs > 1 else 1
         self.msg_mode = int(opt.msg_mode)
@@ -409,6 +459,10 @@ class WitnessEngine:
     def compact_bytes(self):
         """Bytes of one batch in compact wire form (bit-packed SHA witnesses + staged field witnesses, ~2.6 MB per instance)."""
         return self._counter(lib().blsw_engine_compact_bytes)
+
+    def compact_layout(self):
+        """blsw_compact_layout_t of this engine's compact steps (ConstraintChecker.which_is_unsatisfied_compact reads a step through it)"""
+        return compact_layout(self.n, self.msg_len, _opt=self._opt)
 
     def new_compact_buffer(self, batches=1):
         import torch
@@ -1024,6 +1078,58 @@ class ConstraintChecker:
         rc = lib().blsw_r1cs_evaluate(self._r, ip, ist, wp, ws, n, form, begin, count, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), s.cuda_stream)
         if rc:
             raise BlswError("blsw_r1cs_evaluate failed: %d" % rc)
+        return tuple(out)
+
+    def _io_compact(self, layout, compact, instance, stream):
+        """-> (n, instance pointer, instance stride, stream) for a step's compact buffer (uint8 cuda tensor of layout.total bytes)"""
+        torch = self.torch
+        assert isinstance(layout, blsw_compact_layout_t)
+        assert compact.is_cuda and compact.device == self.device and compact.is_contiguous() and compact.dtype.itemsize == 1 and compact.numel() >= layout.total
+        n, ip, ist = int(layout.n), None, 0
+        if instance is not None:
+            assert instance.is_cuda and instance.device == self.device and instance.dtype == torch.int64 and instance.dim() == 3 and instance.shape[2] == 6
+            assert instance.stride(2) == 1 and instance.stride(1) == 6 and instance.stride(0) % 6 == 0 and instance.shape[0] == n and instance.shape[1] >= self.n_instance_vars
+            ip, ist = instance.data_ptr(), instance.stride(0) // 6
+        elif self.n_instance_vars > 1:
+            raise BlswError("this circuit has %d public inputs and the compact form carries witnesses only: pass instance=" % (self.n_instance_vars - 1))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if s != torch.cuda.current_stream(self.device):
+            self.buffer.record_stream(s)
+        return n, ip, ist, s
+
+    def _check_compact(self, layout, compact, instance, stream, want_unreduced):
+        n, ip, ist, s = self._io_compact(layout, compact, instance, stream)
+        with self.torch.cuda.stream(s):
+            bad = self.torch.empty(n, dtype=self.torch.int64, device=self.device)
+            unr = self.torch.empty(n, dtype=self.torch.int64, device=self.device) if want_unreduced else None
+        rc = lib().blsw_r1cs_check_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, bad.data_ptr(), unr.data_ptr() if unr is not None else None, s.cuda_stream)
+        if rc:
+            raise BlswError("blsw_r1cs_check_compact failed: %d" % rc)
+        return bad, unr
+
+    def which_is_unsatisfied_compact(self, layout, compact, instance=None, stream=None):
+        """which_is_unsatisfied of the layout.n instances of a step read straight from its compact buffer (WitnessEngine.submit_compact /
+        compact_layout()): no expand_compact, no 34 MB-per-instance tensor. Montgomery form; instance as in which_is_unsatisfied."""
+        return self._check_compact(layout, compact, instance, stream, False)[0]
+
+    def is_satisfied_compact(self, layout, compact, instance=None, stream=None):
+        """bool [layout.n]"""
+        return self.which_is_unsatisfied_compact(layout, compact, instance, stream) < 0
+
+    def first_unreduced_compact(self, layout, compact, instance=None, stream=None):
+        """int64 [layout.n]: first index of z = [instance | witness] >= p among the instance vector and the staged rows (a bit cannot be), or -1"""
+        return self._check_compact(layout, compact, instance, stream, True)[1]
+
+    def evaluate_compact(self, layout, compact, instance=None, rows=None, stream=None):
+        """evaluate() with z read from a step's compact buffer: (az, bz, cz), int64 [layout.n, count, 6] each, Montgomery form"""
+        begin, count = rows if rows is not None else (0, self.n_constraints)
+        n, ip, ist, s = self._io_compact(layout, compact, instance, stream)
+        with self.torch.cuda.stream(s):
+            out = [self.torch.empty((n, count, 6), dtype=self.torch.int64, device=self.device) for _ in range(3)]
+        rc = lib().blsw_r1cs_evaluate_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, begin, count, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                              s.cuda_stream)
+        if rc:
+            raise BlswError("blsw_r1cs_evaluate_compact failed: %d" % rc)
         return tuple(out)
 
 

@@ -177,8 +177,9 @@ static void launch_place(blsw_engine* e, hipStream_t st, const Fp* staging, cons
     const uint32_t rows = e->L.n_witness - e->L.sha_bits;
     const unsigned chunks = (rows * 3 + 256 * BLSW_PLACE_ITERS - 1) / (256 * BLSW_PLACE_ITERS);
     dim3 grid2(8 * ((chunks + 7) / 8) * (unsigned)e->n);
+    const MovedSegment mv = moved_segment(e->L, e->modes);
     hipLaunchKernelGGL(k_place_field, grid2, dim3(256), 0, st, staging, pair, first, e->L.off_expand, e->L.sha_bits, rows, split_row, out, out_stride, (uint32_t)e->n,
-                       e->L.off_sig_alloc, e->modes.g2_team ? e->L.off_pk_not_zero - e->L.off_sig_alloc : 0u, e->LS.off_sig_alloc);
+                       mv.lo, mv.len, mv.at);
 }
 // N+1-pair product: a step's pair tiles, instance tiles and instance-major rows -> their places in the n instance vectors. Sources: the
 // group workspace (first lanes of the step given) or a compact buffer (first lanes 0, instance tiles tile_w wide)
@@ -908,6 +909,20 @@ int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, 
 int blsw_engine_compact_bytes(blsw_engine_t* e, uint64_t* bytes) {
     if (!e || !bytes || !e->staged || !compact_shape_ok(e->n, e->L.n_pairs)) return BLSW_ERR_ARG;
     *bytes = compact_form(e->n, carve(nullptr, e->n * e->L.n_pairs, e->L, true, e->modes, e->n), e->L.n_pairs).total;
+    return BLSW_OK;
+}
+// the compact steps of a staged engine of these arguments, described for a consumer (blsw_r1cs_check_compact); host only
+int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, blsw_compact_layout_t* out) {
+    if (!out || !options || n % 64 || options->n_pairs > 1) return BLSW_ERR_ARG;
+    if (int rc = check_options(n, msg_len, 2, 1, options)) return rc;  // any staged engine: the step's form does not depend on max_steps / n_buffers
+    blsw_layout_t L;
+    options_layout(msg_len, options, &L);
+    *out = compact_layout(n, L, Modes{options->pairing_mode == 0, options->g2_mode == 1});
+    return BLSW_OK;
+}
+int blsw_compact_locate(const blsw_compact_layout_t* layout, uint32_t k, uint64_t lane, uint32_t* region, uint64_t* byte_offset, uint32_t* bit) {
+    if (!layout || !region || !byte_offset || !bit || !compact_layout_ok(*layout) || k >= layout->n_witness || lane >= layout->n) return BLSW_ERR_ARG;
+    *region = compact_locate(*layout, k, lane, byte_offset, bit);
     return BLSW_OK;
 }
 int blsw_engine_submit_compact(blsw_engine_t* e, const uint64_t* d_pk_xy, const uint64_t* d_sig_xy, const uint8_t* d_msg, void* d_compact, int32_t* d_result,

@@ -13,6 +13,11 @@
 //     REDC(A) * REDC(B) * K  ==  REDC(C)      (products in Montgomery form; K = R^2 for Montgomery input, R^3 for canonical input)
 // For Montgomery input (z = v R) REDC gives the canonical row value, for canonical input v R^-1; either way the two sides differ by
 // the same power of R. An empty A or B row skips the products.
+//
+// Two sources of z, one kernel template: expanded witness vectors (Args: [n][stride][6]), or a step's compact wire form (CompactArgs: the engine's
+// bit words and staged rows as they travel, blsw_compact_layout_t). The compact source evaluates compact_locate (kcommon.hpp) per entry: the column is
+// wave-uniform, so region and row are scalar arithmetic and the three-way branch does not diverge; a bit column is one u32 per lane, a tile row one
+// contiguous 3 KB read per wave — the instance-interleaved gather the expanded form cannot give.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,7 +25,7 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/blsw.h"
-#include "fp.hpp"
+#include "kcommon.hpp"
 
 using namespace blsw;
 
@@ -50,6 +55,12 @@ struct Args {
     Fp k;                     // check: R^(3 - form); evaluate: R^2
     uint64_t* bad;            // check: [n] first unsatisfied row (u64 max = none)
     uint64_t* out[3];         // evaluate: [n][row_hi - row_lo][6]
+};
+
+// z from a compact step: lane i of the buffer is instance i; always Montgomery form (a.one = R mod p serves column 0 and the set bits)
+struct CompactArgs : Args {
+    blsw_compact_layout_t c;
+    const char* compact;
 };
 
 struct Acc {
@@ -122,8 +133,25 @@ __device__ __forceinline__ Fp load_z(const Args& a, uint64_t i, uint32_t col) {
     return a.one;
 }
 
+__device__ __forceinline__ Fp load_z(const CompactArgs& a, uint64_t i, uint32_t col) {
+    if (col >= a.n_inst) {
+        uint64_t off;
+        uint32_t bit;
+        const uint64_t lane = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(i >> 6)) << 6) | (i & 63);  // the tile is wave-uniform: scalar address terms
+        if (compact_locate(a.c, col - a.n_inst, lane, &off, &bit) != BLSW_COMPACT_BIT) return load_fp(reinterpret_cast<const uint64_t*>(a.compact + off));
+        const uint32_t m = 0u - ((*reinterpret_cast<const uint32_t*>(a.compact + off) >> bit) & 1u);
+        Fp r;
+#pragma unroll
+        for (int j = 0; j < 12; j++) r.l[j] = a.one.l[j] & m;
+        return r;
+    }
+    if (a.inst) return load_fp(a.inst + (i * a.inst_stride + col) * 6);
+    return a.one;
+}
+
 // REDC(<M_row, z>) of one matrix row
-__device__ __forceinline__ Fp row_dot(const Args& a, int m, uint64_t k0, uint64_t k1, uint64_t i) {
+template <class A>
+__device__ __forceinline__ Fp row_dot(const A& a, int m, uint64_t k0, uint64_t k1, uint64_t i) {
     Acc x;
 #pragma unroll
     for (int j = 0; j < 14; j++) x.l[j] = 0;
@@ -146,8 +174,8 @@ __device__ __forceinline__ Fp row_dot(const Args& a, int m, uint64_t k0, uint64_
     return redc14(x);
 }
 
-template <bool EVAL>
-__global__ __launch_bounds__(64 * WAVES) void k_r1cs(Args a) {
+template <bool EVAL, class A>
+__global__ __launch_bounds__(64 * WAVES) void k_r1cs(A a) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t b = blockIdx.x * WAVES + wave;
     const uint64_t i = (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);
@@ -199,6 +227,26 @@ __global__ __launch_bounds__(256) void k_r1cs_unreduced(const uint64_t* __restri
             atomicMin(out + i, (unsigned long long)k);
             break;
         }
+    }
+}
+
+// the same over the staged rows of a compact step (a bit cannot be unreduced): grid (chunks, 64-instance tiles), lane = instance, a wave takes one
+// staged row at a time — 3 KB contiguous below split_row. j counts the witnesses outside the SHA segment; the moved segment makes a thread's
+// indices non-monotonic, so every hit goes to the atomic.
+__global__ __launch_bounds__(256) void k_r1cs_unreduced_compact(blsw_compact_layout_t c, const char* __restrict__ compact, uint32_t n_inst, unsigned long long* __restrict__ out) {
+    constexpr uint32_t P[12] = BLSW_P_LIMBS;
+    const uint64_t i = (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);
+#pragma unroll 1
+    for (uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6); j < c.staging_rows; j += gridDim.x * 4) {
+        const uint32_t k = j < c.off_expand ? j : j + c.sha_bits;
+        uint64_t off;
+        uint32_t bit;
+        compact_locate(c, k, i, &off, &bit);
+        const Fp z = load_fp(reinterpret_cast<const uint64_t*>(compact + off));
+        uint32_t borrow = 0;
+#pragma unroll
+        for (int l = 0; l < 12; l++) subb32(z.l[l], P[l], borrow);
+        if (!borrow) atomicMin(out + i, (unsigned long long)n_inst + k);
     }
 }
 
@@ -433,10 +481,20 @@ int launch(Args a, bool eval, hipStream_t st) {
             if (base.out[m]) a.out[m] = base.out[m] + first * (base.row_hi - base.row_lo) * 6;
         dim3 grid((a.n_blk + WAVES - 1) / WAVES, (unsigned)((cnt + 63) / 64));
         if (eval)
-            hipLaunchKernelGGL(k_r1cs<true>, grid, dim3(64 * WAVES), 0, st, a);
+            hipLaunchKernelGGL((k_r1cs<true, Args>), grid, dim3(64 * WAVES), 0, st, a);
         else
-            hipLaunchKernelGGL(k_r1cs<false>, grid, dim3(64 * WAVES), 0, st, a);
+            hipLaunchKernelGGL((k_r1cs<false, Args>), grid, dim3(64 * WAVES), 0, st, a);
     }
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+// a compact step is at most 65535 tiles (compact_layout_ok): one launch
+int launch(const CompactArgs& a, bool eval, hipStream_t st) {
+    dim3 grid((a.n_blk + WAVES - 1) / WAVES, (unsigned)(a.n / 64));
+    if (eval)
+        hipLaunchKernelGGL((k_r1cs<true, CompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_r1cs<false, CompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
     return hip_ok(hipGetLastError(), "launch");
 }
 
@@ -453,12 +511,11 @@ struct Guard {
 
 }  // namespace
 
-int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
-                    uint32_t form, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
-    if (io_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form) || !d_first_unsatisfied) return BLSW_ERR_ARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    Guard guard(r->device);
-    Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
+namespace {
+
+// the whole matrix, first unsatisfied row per instance
+template <class A>
+int run_check(const blsw_r1cs* r, A& a, uint32_t form, int64_t* d_first_unsatisfied, hipStream_t st) {
     static constexpr uint32_t R2[12] = BLSW_R2_LIMBS, R3[12] = BLSW_R3_LIMBS;
     a.k = fp_const(form ? R3 : R2);
     a.blk_first = 0;
@@ -466,8 +523,54 @@ int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instanc
     a.row_lo = 0;
     a.row_hi = r->n_cons;
     a.bad = reinterpret_cast<uint64_t*>(d_first_unsatisfied);
-    if (hip_ok(hipMemsetAsync(d_first_unsatisfied, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;  // all ones = -1 = satisfied
-    int rc = launch(a, false, st);
+    if (hip_ok(hipMemsetAsync(d_first_unsatisfied, 0xFF, a.n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;  // all ones = -1 = satisfied
+    return launch(a, false, st);
+}
+// rows [row_begin, row_begin + row_count) of A z, B z, C z
+template <class A>
+int run_evaluate(const blsw_r1cs* r, A& a, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, hipStream_t st) {
+    static constexpr uint32_t R2[12] = BLSW_R2_LIMBS;
+    a.k = fp_const(R2);
+    a.row_lo = row_begin;
+    a.row_hi = row_begin + row_count;
+    // blocks [b0, b1) that hold rows of the range
+    const auto& blk = r->blk;
+    const uint64_t b0 = (uint64_t)(std::upper_bound(blk.begin(), blk.end(), a.row_lo) - blk.begin()) - 1;
+    const uint64_t b1 = (uint64_t)(std::lower_bound(blk.begin(), blk.end(), a.row_hi) - blk.begin());
+    a.blk_first = (uint32_t)b0;
+    a.n_blk = (uint32_t)(b1 - b0);
+    a.out[0] = d_az;
+    a.out[1] = d_bz;
+    a.out[2] = d_cz;
+    return launch(a, true, st);
+}
+bool row_window_ok(const blsw_r1cs* r, uint64_t row_begin, uint64_t row_count) {
+    return row_count != 0 && row_begin < r->n_cons && row_count <= r->n_cons - row_begin;
+}
+// the argument rules of the compact calls (host only), and their arguments
+int compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride) {
+    if (!r || !c || !d_compact || (reinterpret_cast<uintptr_t>(d_compact) & 15) || !compact_layout_ok(*c) || c->n_witness != r->n_wit) return BLSW_ERR_ARG;
+    if (r->n_inst > 1 && (!d_instance || instance_stride < r->n_inst)) return BLSW_ERR_ARG;
+    if (d_instance && instance_stride < r->n_inst) return BLSW_ERR_ARG;
+    return BLSW_OK;
+}
+CompactArgs make_compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride) {
+    CompactArgs a;
+    static_cast<Args&>(a) = make_args(r, d_instance, instance_stride, nullptr, 0, c->n, 0);
+    a.c = *c;
+    a.compact = reinterpret_cast<const char*>(d_compact);
+    return a;
+}
+
+}  // namespace
+
+int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
+                    uint32_t form, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (io_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form) || !d_first_unsatisfied) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
+    int rc = run_check(r, a, form, d_first_unsatisfied, st);
     if (rc || !d_first_unreduced) return rc;
     if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
     const uint64_t n_z = r->n_inst + r->n_wit, chunks = (n_z + 255) / 256;
@@ -484,22 +587,41 @@ int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instanc
 int blsw_r1cs_evaluate(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
                        uint32_t form, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream) {
     if (io_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form) || !d_az || !d_bz || !d_cz) return BLSW_ERR_ARG;
-    if (row_count == 0 || row_begin >= r->n_cons || row_count > r->n_cons - row_begin) return BLSW_ERR_ARG;
+    if (!row_window_ok(r, row_begin, row_count)) return BLSW_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     Guard guard(r->device);
     Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
-    static constexpr uint32_t R2[12] = BLSW_R2_LIMBS;
-    a.k = fp_const(R2);
-    a.row_lo = row_begin;
-    a.row_hi = row_begin + row_count;
-    // blocks [b0, b1) that hold rows of the range
-    const auto& blk = r->blk;
-    const uint64_t b0 = (uint64_t)(std::upper_bound(blk.begin(), blk.end(), a.row_lo) - blk.begin()) - 1;
-    const uint64_t b1 = (uint64_t)(std::lower_bound(blk.begin(), blk.end(), a.row_hi) - blk.begin());
-    a.blk_first = (uint32_t)b0;
-    a.n_blk = (uint32_t)(b1 - b0);
-    a.out[0] = d_az;
-    a.out[1] = d_bz;
-    a.out[2] = d_cz;
-    return launch(a, true, st);
+    return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
+}
+
+int blsw_r1cs_check_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                            int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (compact_args(r, layout, d_compact, d_instance, instance_stride) || !d_first_unsatisfied) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    CompactArgs a = make_compact_args(r, layout, d_compact, d_instance, instance_stride);
+    int rc = run_check(r, a, 0, d_first_unsatisfied, st);
+    if (rc || !d_first_unreduced) return rc;
+    const uint64_t n = layout->n;
+    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
+    unsigned long long* unr = reinterpret_cast<unsigned long long*>(d_first_unreduced);
+    if (d_instance) {  // the instance vectors are plain: the existing pass over the first n_inst indices of z (atomicMin: any order with the rows)
+        for (uint64_t first = 0; first < n; first += 65535) {
+            const uint64_t cnt = n - first < 65535 ? n - first : 65535;
+            hipLaunchKernelGGL(k_r1cs_unreduced, dim3(1, (unsigned)cnt), dim3(256), 0, st, d_instance + first * instance_stride * 6, instance_stride, nullptr, 0,
+                               (uint32_t)r->n_inst, r->n_inst, unr + first);
+        }
+    }
+    const uint32_t chunks = (layout->staging_rows + 3) / 4;
+    if (chunks) hipLaunchKernelGGL(k_r1cs_unreduced_compact, dim3(chunks < 256 ? chunks : 256, (unsigned)(n / 64)), dim3(256), 0, st, *layout, a.compact, (uint32_t)r->n_inst, unr);
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+int blsw_r1cs_evaluate_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                               uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream) {
+    if (compact_args(r, layout, d_compact, d_instance, instance_stride) || !d_az || !d_bz || !d_cz || !row_window_ok(r, row_begin, row_count)) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    CompactArgs a = make_compact_args(r, layout, d_compact, d_instance, instance_stride);
+    return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
 }

@@ -243,6 +243,73 @@ inline CompactForm compact_form(uint64_t n, const Workspace& w, uint32_t K = 1) 
 }
 // can steps of n instances of K pairs leave in compact form (whole pair tiles; instance lanes = whole tiles or an aligned part of one)?
 inline bool compact_shape_ok(uint64_t n, uint32_t K) { return K <= 1 ? n % 64 == 0 : ((n * K) % 64 == 0 && (n % 64 == 0 || 64 % n == 0)); }
+// The segment the g2_team mode stages last: moved_len witnesses that belong at index lo of the vector are staged from row `at` on (len 0: none)
+struct MovedSegment {
+    uint32_t lo, len, at;
+};
+inline MovedSegment moved_segment(const blsw_layout_t& L, const Modes& m) {
+    return {L.off_sig_alloc, m.g2_team ? L.off_pk_not_zero - L.off_sig_alloc : 0u, staging_layout(L, m).off_sig_alloc};
+}
+// blsw_compact_layout_t (include/blsw.h) of the steps of n instances of a single-key or aggregate engine: the carve's and compact_form's numbers
+inline blsw_compact_layout_t compact_layout(uint64_t n, const blsw_layout_t& L, const Modes& m) {
+    const Workspace w = carve(nullptr, n, L, true, m, n);
+    const CompactForm cf = compact_form(n, w);
+    const MovedSegment mv = moved_segment(L, m);
+    blsw_compact_layout_t c;
+    c.n = n;
+    c.off_staging = cf.off_staging;
+    c.off_pair = cf.off_pair;
+    c.total = cf.total;
+    c.n_witness = L.n_witness;
+    c.off_expand = L.off_expand;
+    c.sha_bits = L.sha_bits;
+    c.sha_words = (uint32_t)w.sha_words;
+    c.split_row = w.split_row;
+    c.staging_rows = (uint32_t)w.staging_rows;
+    c.pair_rows = w.pair_rows;
+    c.moved_lo = mv.lo;
+    c.moved_len = mv.len;
+    c.moved_at = mv.at;
+    return c;
+}
+// every access blsw_compact_locate / the compact checker derive from c stays inside [0, c.total) — checked before a caller's struct is used
+inline bool compact_layout_ok(const blsw_compact_layout_t& c) {
+    if (c.n == 0 || c.n % 64 || c.n > 65535ull * 64 || c.sha_bits > c.n_witness || c.off_expand > c.n_witness - c.sha_bits) return false;
+    if (c.staging_rows != c.n_witness - c.sha_bits || c.split_row > c.staging_rows || c.pair_rows != c.staging_rows - c.split_row) return false;
+    if (c.sha_words % BLSW_BITS_CHUNK_WORDS || (uint64_t)c.sha_words * 32 < c.sha_bits) return false;
+    if (c.moved_len && (c.moved_at > c.staging_rows || c.moved_len != c.staging_rows - c.moved_at || c.moved_lo > c.off_expand || c.moved_len > c.off_expand - c.moved_lo))
+        return false;
+    if ((c.off_staging | c.off_pair) & 15) return false;
+    const uint64_t bits = bits_tile_words(c.sha_words) * (c.n / 64) * 4, tiles = (uint64_t)c.split_row * c.n * sizeof(Fp), rows = (uint64_t)c.pair_rows * c.n * sizeof(Fp);
+    return c.off_staging >= bits && c.off_pair >= c.off_staging && c.off_pair - c.off_staging >= tiles && c.total >= c.off_pair && c.total - c.off_pair >= rows;
+}
+// Where witness k of instance `lane` lives in a compact buffer: the inverse of k_place_field's row -> index rule (the SHA segment is cut out of the
+// staged rows; a moved segment is staged last) followed by the addressing of the three regions. Returns BLSW_COMPACT_*; *byte_offset is the u32
+// word of the bit (*bit = its position) or the element. k is wave-uniform in the checker, so region and row are scalar; only the lane term is not.
+BLSW_HD uint32_t compact_locate(const blsw_compact_layout_t& c, uint32_t k, uint64_t lane, uint64_t* byte_offset, uint32_t* bit) {
+    const uint64_t tile = lane >> 6, l = lane & 63;
+    *bit = 0;
+    if (k >= c.off_expand && k - c.off_expand < c.sha_bits) {
+        const uint32_t b = k - c.off_expand, w = b >> 5;
+        *bit = b & 31;
+        *byte_offset = (tile * bits_tile_words(c.sha_words) + (uint64_t)(w / BLSW_BITS_CHUNK_WORDS) * (64 * BLSW_BITS_CHUNK_WORDS) + l * BLSW_BITS_CHUNK_WORDS +
+                        w % BLSW_BITS_CHUNK_WORDS) * 4;
+        return BLSW_COMPACT_BIT;
+    }
+    uint32_t row;
+    if (c.moved_len && k >= c.moved_lo && k - c.moved_lo < c.moved_len) {
+        row = c.moved_at + (k - c.moved_lo);
+    } else {
+        row = k < c.off_expand ? k : k - c.sha_bits;
+        if (c.moved_len && row >= c.moved_lo) row -= c.moved_len;
+    }
+    if (row < c.split_row) {
+        *byte_offset = c.off_staging + ((tile * c.split_row + row) * 64 + l) * sizeof(Fp);
+        return BLSW_COMPACT_TILE;
+    }
+    *byte_offset = c.off_pair + (lane * c.pair_rows + (row - c.split_row)) * sizeof(Fp);
+    return BLSW_COMPACT_PAIR;
+}
 // a group of `steps` batches of n instances each, processed by one set of launches (N = steps * n * K lanes per chain;
 // K = (pk, msg) pairs per instance: 1 except for the N+1-pair product)
 struct Group {

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 13
+#define BLSW_ABI_VERSION 14
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -328,6 +328,29 @@ int blsw_engine_submit_aggregate_compact(blsw_engine_t* e, const uint64_t* d_pks
 int blsw_engine_submit_multi_compact(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_msgs, const uint64_t* d_sig_xy, void* d_compact, int32_t* d_result,
                                      void* stream);
 int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream);
+/* ABI 14: where a witness element lives in a compact buffer — what a consumer needs to read a step without expanding it (blsw_r1cs_check_compact).
+ * A compact step of n instances (n a multiple of 64; instance i is lane i & 63 of tile i / 64) is three regions back to back:
+ *   bit words   [n/64][sha_words/16][64][16] u32 at offset 0: witness off_expand + b (b < sha_bits) is bit b & 31 of word b / 32 of the lane's stream
+ *   tile rows   [n/64][split_row][64] elements at off_staging: staged row r < split_row of a lane
+ *   pair rows   [n][pair_rows] elements at off_pair: staged row split_row + r of a lane (the pairing segments, instance-major)
+ * Staged rows are the witness vector with the SHA segment cut out (staging_rows = n_witness - sha_bits); with options.g2_mode 1 the moved_len
+ * witnesses from moved_lo on are staged last, from row moved_at on (moved_len 0 otherwise). Elements are always Montgomery form.
+ * The N+1-pair product's compact form (pair tiles and instance tiles) is not described by this struct. */
+typedef struct {
+    uint64_t n, off_staging, off_pair, total; /* instances of the step; byte offsets of the two row regions; bytes of the step */
+    uint32_t n_witness, off_expand, sha_bits, sha_words, split_row, staging_rows, pair_rows, moved_lo, moved_len, moved_at;
+} blsw_compact_layout_t;
+#define BLSW_COMPACT_BIT 0  /* regions blsw_compact_locate reports */
+#define BLSW_COMPACT_TILE 1
+#define BLSW_COMPACT_PAIR 2
+/* The layout of the compact steps of an engine created with (n, msg_len, options) — any staged engine: max_steps and n_buffers do not enter.
+ * total == blsw_engine_compact_bytes of such an engine. BLSW_ERR_ARG: a NULL pointer, n % 64 != 0, options.n_pairs > 1, and every option set
+ * blsw_engine_create_ex refuses for a staged engine. Host only. */
+int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, blsw_compact_layout_t* out);
+/* witness k (< n_witness) of instance `lane` (< n) of a compact step: *region = BLSW_COMPACT_*; *byte_offset = offset in the buffer of the u32 word
+ * that holds the bit (then *bit = its position in the word, LSB = 0) or of the element's 48 bytes (*bit = 0). The one statement of the rule:
+ * the device checker evaluates the same function. BLSW_ERR_ARG: a NULL pointer, k or lane out of range, an inconsistent layout. Host only. */
+int blsw_compact_locate(const blsw_compact_layout_t* layout, uint32_t k, uint64_t lane, uint32_t* region, uint64_t* byte_offset, uint32_t* bit);
 /* average duration (ms) of the bit->Fp expansion kernel launches issued since the previous call (HIP events on the stream they
  * ran on, at most 1024 launches); blocks until they have finished and resets the statistics */
 int blsw_engine_expand_stats(blsw_engine_t* e, uint32_t* count, float* avg_ms);
@@ -407,6 +430,17 @@ int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instanc
 /* rows [row_begin, row_begin + row_count): d_az / d_bz / d_cz [n][row_count][6] u64 = <A_j, z>, <B_j, z>, <C_j, z> reduced, in the input's form */
 int blsw_r1cs_evaluate(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instance_stride, const uint64_t* d_witness, uint64_t witness_stride, uint64_t n,
                        uint32_t form, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
+/* ABI 14: the same two calls with z read straight from a step's compact buffer (blsw_compact_layout_t above; d_compact 16-byte aligned, layout->total
+ * bytes) instead of from expanded witness vectors: n = layout->n instances, results and conventions as blsw_r1cs_check / _evaluate. A receiver validates
+ * a step without blsw_engine_expand_compact and without the 34 MB-per-instance tensor. The compact form carries witnesses only: d_instance
+ * [n][instance_stride] as above (required when n_instance_vars > 1). Elements are Montgomery form (form 0). d_first_unreduced reads the staged rows
+ * only (a bit cannot be unreduced) and reports n_instance_vars + k for witness k. BLSW_ERR_ARG before any launch, nothing written: a NULL handle,
+ * layout, buffer or output, layout->n_witness != the handle's, n % 64 != 0 or an inconsistent layout, a missing instance vector or
+ * instance_stride < n_instance_vars, a row range outside the matrix. */
+int blsw_r1cs_check_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                            int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+int blsw_r1cs_evaluate_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                               uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
 
 /* Input decode (PublicKey::try_from / Signature::try_from -> deserialize_compressed, src/bls.rs:219-242, 316-339):
  *   d_pk48 [n][48], d_sig96 [n][96]  ZCash-format compressed points

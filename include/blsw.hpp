@@ -153,6 +153,23 @@ class ConstraintSystem {
         d_bad.download(bad.data(), n_ * 8);
         return bad;
     }
+    // The same for a step of this circuit shape in compact wire form (blsw_r1cs_check_compact): d_compact is a device buffer of layout.total bytes —
+    // a step another rank's engine produced with blsw_engine_submit_compact — and layout its blsw_compact_layout; layout.n verdicts. The step is
+    // read where it lies: no blsw_engine_expand_compact, no witness vectors. A circuit with public inputs takes d_instance [layout.n][n_instance_vars][6]
+    // (device; the compact form carries witnesses only), by default the instance vectors this object's verify wrote (then layout.n == n).
+    std::vector<int64_t> which_is_unsatisfied(const blsw_compact_layout_t& layout, const void* d_compact, const uint64_t* d_instance = nullptr) {
+        if (!r1cs_) build_checker();
+        if (layout_.n_instance_vars > 1 && !d_instance) {
+            if (!instance_.get() || layout.n != n_) throw Error("which_is_unsatisfied(compact): instance vectors of layout.n systems", BLSW_ERR_ARG);
+            d_instance = static_cast<const uint64_t*>(instance_.get());
+        }
+        detail::DeviceBytes d_bad(layout.n * 8);
+        check(blsw_r1cs_check_compact(r1cs_, &layout, d_compact, d_instance, d_instance ? layout_.n_instance_vars : 0, static_cast<int64_t*>(d_bad.get()), nullptr, nullptr),
+              "blsw_r1cs_check_compact");
+        std::vector<int64_t> bad(layout.n);
+        d_bad.download(bad.data(), layout.n * 8);
+        return bad;
+    }
     // cs.is_satisfied() of system i (one check of all n systems per call: call which_is_unsatisfied() once for a whole batch)
     bool is_satisfied(size_t i) {
         if (i >= n_) throw Error("is_satisfied out of range", BLSW_ERR_ARG);

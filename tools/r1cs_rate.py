@@ -6,7 +6,15 @@
     products_per_instance                       product-equivalents counted from the encoded class histogram (a table coefficient = 1,
                                                 a row = 3 reductions of half a product + 2 products), and the rate that implies
 
-    python tools/r1cs_rate.py [--n 1024] [--reps 3] [--eval-n 64]"""
+    python tools/r1cs_rate.py [--n 1024] [--reps 3] [--eval-n 64]
+
+--compact: from a step in compact wire form to a verdict, two legs interleaved in one process over the same compact steps (HIP-event time per
+call; median / min / max of --reps >= 5 calls each):
+    expand_then_check   blsw_engine_expand_compact into n witness vectors, then blsw_r1cs_check on them (the only route before ABI 14)
+    check_compact       blsw_r1cs_check_compact on the buffer itself
+and the same pair for A z, B z, C z over a window of --eval-rows rows at the pairing tail (expand + evaluate / evaluate_compact).
+
+    python tools/r1cs_rate.py --compact [--n 1024] [--reps 5] [--steps 2] [--eval-rows 20000]"""
 import argparse
 import importlib
 import json
@@ -38,12 +46,96 @@ def class_histogram(mats):
     return h
 
 
+def stats(ms, n):
+    ms = sorted(ms)
+    med = ms[len(ms) // 2] if len(ms) % 2 else 0.5 * (ms[len(ms) // 2 - 1] + ms[len(ms) // 2])
+    return {"median_ms": round(med, 3), "min_ms": round(ms[0], 3), "max_ms": round(ms[-1], 3), "calls": len(ms), "instances_per_s": round(n / (med / 1e3), 1)}
+
+
+def compact_legs(a):
+    """--compact: the two routes from compact steps to a verdict, alternating, over the same steps of the grouped engine"""
+    import torch
+
+    pkg = importlib.import_module("bls-verify-gadget_amd")
+    workload = importlib.import_module("bls-verify-gadget_amd.workload")
+    dev = torch.device("cuda:0")
+    reps = max(5, a.reps)
+    mats = pkg.matrices(32)
+    chk = pkg.ConstraintChecker.from_matrices(mats, dev)
+    eng = pkg.WitnessEngine(a.n, 32, max_steps=16, device=dev, n_buffers=3)
+    lay = eng.compact_layout()
+    assert lay.total == eng.compact_bytes()
+    comp = eng.new_compact_buffer(a.steps)
+    batches = [workload.make_batch(pkg, a.n, device=dev, start=s * a.n) for s in range(a.steps)]
+    for s, (pk, msg, sig, _) in enumerate(batches):
+        eng.submit_compact(pk, sig, msg, comp[s])
+    eng.flush()
+    torch.cuda.synchronize()
+    w = eng.new_witness_tensor()  # the receiver's n vectors of 34 MB (leg a only)
+    nc = int(mats["n_constraints"])
+    rows = (nc - a.eval_rows, a.eval_rows)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def leg_a(s):
+        eng.expand_compact(comp[s], w)
+        return chk.which_is_unsatisfied(w)
+
+    def leg_b(s):
+        return chk.which_is_unsatisfied_compact(lay, comp[s])
+
+    def eval_a(s):
+        eng.expand_compact(comp[s], w)
+        return chk.evaluate(w, rows=rows)
+
+    def eval_b(s):
+        return chk.evaluate_compact(lay, comp[s], rows=rows)
+
+    legs = {"expand_then_check": leg_a, "check_compact": leg_b, "expand_then_evaluate": eval_a, "evaluate_compact": eval_b}
+    ms = {k: [] for k in legs}
+    same = True
+    for pair in (("expand_then_check", "check_compact"), ("expand_then_evaluate", "evaluate_compact")):
+        for k in pair:  # warm-up of both legs
+            legs[k](0)
+        torch.cuda.synchronize()
+        for r in range(reps):
+            s = r % a.steps
+            outs = []
+            for k in pair:  # alternating: a, b, a, b, ...
+                t, out = timed(lambda: legs[k](s))
+                ms[k].append(t)
+                outs.append(out)
+            if pair[0] == "expand_then_check":
+                same = same and torch.equal(outs[0], outs[1]) and bool((outs[1] < 0).all())
+            else:
+                same = same and all(torch.equal(x, y) for x, y in zip(outs[0], outs[1]))
+            del outs
+    eng.close()
+    out = {"metric": "r1cs_check_compact_single_key", "n": a.n, "steps": a.steps, "eval_rows": a.eval_rows, "legs_agree_and_satisfied": same,
+           "compact_bytes_per_instance": lay.total // a.n, "expanded_bytes_per_instance": int(mats["n_witness"]) * 48}
+    out.update({k: stats(v, a.n) for k, v in ms.items()})
+    out["check_compact_over_expand_then_check"] = round(out["check_compact"]["median_ms"] / out["expand_then_check"]["median_ms"], 3)
+    out["check_compact_share_of_10k_per_s"] = round(out["check_compact"]["instances_per_s"] / 1e4, 3)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--eval-n", type=int, default=64)
+    ap.add_argument("--compact", action="store_true", help="expand_compact + check against check_compact, interleaved (see the module docstring)")
+    ap.add_argument("--steps", type=int, default=2, help="--compact: distinct compact steps the calls rotate over")
+    ap.add_argument("--eval-rows", type=int, default=20000, help="--compact: rows of the evaluate window (the pairing tail)")
     a = ap.parse_args()
+    if a.compact:
+        return compact_legs(a)
     import torch
 
     pkg = importlib.import_module("bls-verify-gadget_amd")
