@@ -22,24 +22,19 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <unordered_map>
 #include <vector>
 #include "../../include/blsw.h"
 #include "kcommon.hpp"
+#include "r1cs_encode.hpp"  // the host's validation, coefficient classes and block cut; r1cs_row.hpp: the accumulator, row_term, redc14
 
 using namespace blsw;
+using namespace blsw::r1cs;
 
 namespace {
 
-constexpr uint32_t CLS_POS = 0u, CLS_NEG = 1u, CLS_GEN = 2u;
-constexpr uint32_t PAYLOAD_BITS = 30, PAYLOAD = (1u << PAYLOAD_BITS) - 1;
-constexpr int WAVES = 4;  // waves (row blocks) per workgroup
-// block cut: work units of an entry by class, of a row's reductions and comparison, and per block
-constexpr uint64_t W_ONE = 2, W_SMALL = 3, W_GEN = 10, W_ROW = 30, W_BLOCK = 16384;
-
 struct Enc {
     const uint64_t* rp[3];   // row pointers [n_constraints + 1]
-    const uint2* ent[3];     // {column, code} [nnz]
+    const blsw_u2* ent[3];   // {column, code} [nnz]
     const Fp* table;         // distinct Montgomery coefficients of class GEN
     const uint64_t* blk;     // first row of every block [n_blocks + 1]
 };
@@ -62,64 +57,6 @@ struct CompactArgs : Args {
     blsw_compact_layout_t c;
     const char* compact;
 };
-
-struct Acc {
-    uint32_t l[14];
-};
-
-__device__ __forceinline__ void acc_add(Acc& x, const Fp& v) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) x.l[i] = addc32(x.l[i], v.l[i], c);
-    x.l[12] = addc32(x.l[12], 0, c);
-    x.l[13] += c;
-}
-// x += v * z, v < 2^30
-__device__ __forceinline__ void acc_add_small(Acc& x, const Fp& z, uint32_t v) {
-    uint32_t hi = 0, c = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        const uint64_t t = (uint64_t)z.l[i] * v + hi;
-        hi = (uint32_t)(t >> 32);
-        x.l[i] = addc32(x.l[i], (uint32_t)t, c);
-    }
-    x.l[12] = addc32(x.l[12], hi, c);
-    x.l[13] += c;
-}
-// p - z (z <= p: a representative of -z below 2^381; 0 gives p, which the reduction absorbs)
-__device__ __forceinline__ Fp neg_raw(const Fp& z) {
-    constexpr uint32_t P[12] = BLSW_P_LIMBS;
-    Fp r;
-    uint32_t b = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) r.l[i] = subb32(P[i], z.l[i], b);
-    return r;
-}
-// Montgomery reduction of the 448-bit sum: X 2^-384 mod p. X < 2^443 (a row of < 2^32 terms below 2^411), so every partial value
-// (X + M p) / 2^(32 i) stays below 2^448 and the result below p + 2^59 < 2p.
-__device__ __noinline__ Fp redc14(Acc x) {
-    constexpr uint32_t P[12] = BLSW_P_LIMBS;
-    uint32_t* t = x.l;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        const uint32_t m = t[0] * BLSW_INV32;
-        uint64_t s = (uint64_t)m * P[0] + t[0];  // low word 0
-#pragma unroll
-        for (int j = 1; j < 12; j++) {
-            s = (uint64_t)m * P[j] + t[j] + (s >> 32);
-            t[j - 1] = (uint32_t)s;
-        }
-        s = (uint64_t)t[12] + (s >> 32);
-        t[11] = (uint32_t)s;
-        s = (uint64_t)t[13] + (s >> 32);
-        t[12] = (uint32_t)s;
-        t[13] = (uint32_t)(s >> 32);
-    }
-    Fp r;
-#pragma unroll
-    for (int i = 0; i < 12; i++) r.l[i] = t[i];
-    return fp_cond_sub_p(r, t[12]);
-}
 
 __device__ __forceinline__ Fp load_fp(const uint64_t* src) {
     const uint4* q = reinterpret_cast<const uint4*>(src);
@@ -155,21 +92,11 @@ __device__ __forceinline__ Fp row_dot(const A& a, int m, uint64_t k0, uint64_t k
     Acc x;
 #pragma unroll
     for (int j = 0; j < 14; j++) x.l[j] = 0;
-    const uint2* ent = a.e.ent[m];
+    const blsw_u2* ent = a.e.ent[m];
 #pragma unroll 1
     for (uint64_t k = k0; k < k1; k++) {
-        const uint2 e = ent[k];
-        const Fp z = load_z(a, i, e.x);
-        const uint32_t cls = e.y >> PAYLOAD_BITS, v = e.y & PAYLOAD;
-        if (cls == CLS_GEN) {
-            acc_add(x, fp_mul(z, a.e.table[v]));
-        } else {
-            const Fp s = cls == CLS_NEG ? neg_raw(z) : z;
-            if (v == 1)
-                acc_add(x, s);
-            else
-                acc_add_small(x, s, v);
-        }
+        const blsw_u2 e = ent[k];
+        row_term(x, load_z(a, i, e.x), e.y, a.e.table);
     }
     return redc14(x);
 }
@@ -259,119 +186,6 @@ int hip_ok(hipError_t e, const char* what) {
     return BLSW_OK;
 }
 
-struct Key {
-    uint64_t w[6];
-    bool operator==(const Key& o) const { return memcmp(w, o.w, sizeof(w)) == 0; }
-};
-struct KeyHash {
-    size_t operator()(const Key& k) const {
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (int i = 0; i < 6; i++) h = (h ^ k.w[i]) * 0xBF58476D1CE4E5B9ull;
-        return (size_t)(h ^ (h >> 31));
-    }
-};
-
-// value < p and != 0 (6 little-endian u64 limbs)
-bool coefficient_ok(const uint64_t* v) {
-    static const uint64_t P64[6] = {0xb9feffffffffaaabull, 0x1eabfffeb153ffffull, 0x6730d2a0f6b0f624ull, 0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull,
-                                    0x1a0111ea397fe69aull};
-    if ((v[0] | v[1] | v[2] | v[3] | v[4] | v[5]) == 0) return false;
-    for (int i = 5; i >= 0; i--)
-        if (v[i] != P64[i]) return v[i] < P64[i];
-    return false;  // == p
-}
-
-struct Encoded {
-    std::vector<uint2> ent[3];
-    std::vector<Fp> table;
-    std::vector<uint64_t> blk;
-    uint64_t bytes = 0, off_rp[3] = {}, off_ent[3] = {}, off_table = 0, off_blk = 0;
-};
-
-uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
-
-// validates the CSR (include/blsw.h: blsw_r1cs_create) and encodes it; BLSW_ERR_ARG on the first rule it breaks
-int encode(const blsw_matrices_info_t* info, const blsw_matrices_t* m, Encoded* out) {
-    if (!info || !m || info->n_constraints == 0 || info->n_instance_vars == 0) return BLSW_ERR_ARG;
-    const uint64_t n_cons = info->n_constraints, n_z = info->n_instance_vars + info->n_witness;
-    if (n_z > 0xFFFFFFFFull) return BLSW_ERR_ARG;  // u32 columns
-    std::unordered_map<Key, uint32_t, KeyHash> codes;
-    std::vector<uint64_t> row_work(n_cons, W_ROW);
-    for (int mi = 0; mi < 3; mi++) {
-        const uint64_t* rp = m->row_ptr[mi];
-        const uint32_t* col = m->col[mi];
-        const uint64_t* val = m->val[mi];
-        const uint64_t nnz = info->nnz[mi];
-        if (!rp || (nnz && (!col || !val)) || rp[0] != 0 || rp[n_cons] != nnz) return BLSW_ERR_ARG;
-        std::vector<uint2>& ent = out->ent[mi];
-        ent.resize(nnz);
-        for (uint64_t r = 0; r < n_cons; r++) {
-            if (rp[r + 1] < rp[r] || rp[r + 1] > nnz) return BLSW_ERR_ARG;
-            for (uint64_t k = rp[r]; k < rp[r + 1]; k++) {
-                if (col[k] >= n_z || (k > rp[r] && col[k] <= col[k - 1])) return BLSW_ERR_ARG;
-                const uint64_t* v = val + k * 6;
-                if (!coefficient_ok(v)) return BLSW_ERR_ARG;
-                Key key;
-                memcpy(key.w, v, sizeof(key.w));
-                auto it = codes.find(key);
-                uint32_t code;
-                if (it != codes.end()) {
-                    code = it->second;
-                } else {  // canonical value c = v R^-1: +-c small, or a table entry
-                    Fp mont, one = fp_zero();
-                    memcpy(mont.l, v, sizeof(mont.l));
-                    one.l[0] = 1;
-                    const Fp c = fp_mul(mont, one), nc = fp_neg(c);
-                    auto small = [](const Fp& x) {
-                        uint32_t hi = 0;
-                        for (int j = 1; j < 12; j++) hi |= x.l[j];
-                        return hi == 0 && x.l[0] <= PAYLOAD;
-                    };
-                    if (small(c)) {
-                        code = CLS_POS << PAYLOAD_BITS | c.l[0];
-                    } else if (small(nc)) {
-                        code = CLS_NEG << PAYLOAD_BITS | nc.l[0];
-                    } else {
-                        if (out->table.size() > PAYLOAD) return BLSW_ERR_ARG;
-                        code = CLS_GEN << PAYLOAD_BITS | (uint32_t)out->table.size();
-                        out->table.push_back(mont);
-                    }
-                    codes.emplace(key, code);
-                }
-                ent[k] = make_uint2(col[k], code);
-                const uint32_t cls = code >> PAYLOAD_BITS, pv = code & PAYLOAD;
-                row_work[r] += cls == CLS_GEN ? W_GEN : (pv == 1 ? W_ONE : W_SMALL);
-            }
-        }
-    }
-    // blocks of about W_BLOCK work units (a row longer than that is a block of its own)
-    out->blk.assign(1, 0);
-    uint64_t acc = 0;
-    for (uint64_t r = 0; r < n_cons; r++) {
-        if (acc && acc + row_work[r] > W_BLOCK) {
-            out->blk.push_back(r);
-            acc = 0;
-        }
-        acc += row_work[r];
-    }
-    out->blk.push_back(n_cons);
-    if (out->blk.size() - 1 > 0xFFFFFFFFull / WAVES) return BLSW_ERR_ARG;
-    uint64_t off = 0;
-    for (int mi = 0; mi < 3; mi++) {
-        out->off_rp[mi] = off;
-        off = align256(off + (n_cons + 1) * 8);
-    }
-    for (int mi = 0; mi < 3; mi++) {
-        out->off_ent[mi] = off;
-        off = align256(off + info->nnz[mi] * 8);
-    }
-    out->off_table = off;
-    off = align256(off + out->table.size() * sizeof(Fp));
-    out->off_blk = off;
-    out->bytes = align256(off + out->blk.size() * 8);
-    return BLSW_OK;
-}
-
 }  // namespace
 
 struct blsw_r1cs {
@@ -408,7 +222,7 @@ int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const 
         return bytes ? hip_ok(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync") : BLSW_OK;
     };
     for (int mi = 0; mi < 3 && !rc; mi++) rc = put(e.off_rp[mi], m->row_ptr[mi], (info->n_constraints + 1) * 8);
-    for (int mi = 0; mi < 3 && !rc; mi++) rc = put(e.off_ent[mi], e.ent[mi].data(), e.ent[mi].size() * sizeof(uint2));
+    for (int mi = 0; mi < 3 && !rc; mi++) rc = put(e.off_ent[mi], e.ent[mi].data(), e.ent[mi].size() * sizeof(blsw_u2));
     if (!rc) rc = put(e.off_table, e.table.data(), e.table.size() * sizeof(Fp));
     if (!rc) rc = put(e.off_blk, e.blk.data(), e.blk.size() * 8);
     if (!rc) rc = hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");  // the host vectors go out of scope
@@ -421,7 +235,7 @@ int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const 
     r->n_wit = info->n_witness;
     for (int mi = 0; mi < 3; mi++) {
         r->enc.rp[mi] = reinterpret_cast<const uint64_t*>(base + e.off_rp[mi]);
-        r->enc.ent[mi] = reinterpret_cast<const uint2*>(base + e.off_ent[mi]);
+        r->enc.ent[mi] = reinterpret_cast<const blsw_u2*>(base + e.off_ent[mi]);
     }
     r->enc.table = reinterpret_cast<const Fp*>(base + e.off_table);
     r->enc.blk = reinterpret_cast<const uint64_t*>(base + e.off_blk);

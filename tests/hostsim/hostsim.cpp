@@ -14,6 +14,7 @@
 #include "../../bls-verify-gadget_amd/csrc/cofactor_vf.hpp"
 #include "../../bls-verify-gadget_amd/csrc/prepare_vf.hpp"
 #include "../../bls-verify-gadget_amd/csrc/vpairing.hpp"
+#include "../../bls-verify-gadget_amd/csrc/r1cs_encode.hpp"
 #include <array>
 
 using namespace blsw;
@@ -620,5 +621,47 @@ void hostsim_fp_inv(const uint64_t* a, uint64_t* r) {
 void hostsim_fp_inv_fermat(const uint64_t* a, uint64_t* r) {
     Fp z = fp_inv_fermat(load_fp(a));
     memcpy(r, z.l, 48);
+}
+// the device R1CS evaluator's encoder (r1cs_encode.hpp: what blsw_r1cs_device_bytes / blsw_r1cs_create run). codes[m]: nnz[m] entry codes;
+// table: room for nnz[0] + nnz[1] + nnz[2] elements of 6 u64, *table_size written; blk: room for n_constraints + 1 block starts, *n_blk = the
+// number of blocks (blk[n_blk] = n_constraints). Returns encode()'s code, the outputs written only on BLSW_OK.
+int hostsim_r1cs_encode(uint64_t n_cons, uint64_t n_inst, uint64_t n_wit, const uint64_t* nnz, const uint64_t* const* row_ptr, const uint32_t* const* col,
+                        const uint64_t* const* val, uint32_t* const* codes, uint64_t* table, uint64_t* table_size, uint64_t* blk, uint64_t* n_blk, uint64_t* bytes) {
+    blsw_matrices_info_t info;
+    blsw_matrices_t m;
+    memset(&info, 0, sizeof(info));
+    memset(&m, 0, sizeof(m));
+    info.n_constraints = n_cons;
+    info.n_instance_vars = n_inst;
+    info.n_witness = n_wit;
+    for (int k = 0; k < 3; k++) {
+        info.nnz[k] = nnz[k];
+        m.row_ptr[k] = const_cast<uint64_t*>(row_ptr[k]);
+        m.col[k] = const_cast<uint32_t*>(col[k]);
+        m.val[k] = const_cast<uint64_t*>(val[k]);
+    }
+    r1cs::Encoded e;
+    const int rc = r1cs::encode(&info, &m, &e);
+    if (rc) return rc;
+    for (int k = 0; k < 3; k++)
+        for (uint64_t j = 0; j < nnz[k]; j++) {
+            if (e.ent[k][j].x != col[k][j]) return -1;  // an entry keeps its column
+            codes[k][j] = e.ent[k][j].y;
+        }
+    if (e.table.size()) memcpy(table, e.table.data(), e.table.size() * sizeof(Fp));
+    *table_size = e.table.size();
+    memcpy(blk, e.blk.data(), e.blk.size() * 8);
+    *n_blk = e.blk.size() - 1;
+    *bytes = e.bytes;
+    return rc;
+}
+// REDC(<row, z>) of one encoded matrix row by the kernel's own functions (r1cs_row.hpp: row_term per entry, then redc14): count entries
+// (col, code), the table of hostsim_r1cs_encode, z = [n_z][6] stored integers (any value below 2^384: the kernel does not reduce its input)
+void hostsim_r1cs_row(const uint32_t* col, const uint32_t* code, uint64_t count, const uint64_t* table, const uint64_t* z, uint64_t* out) {
+    r1cs::Acc x;
+    for (int j = 0; j < 14; j++) x.l[j] = 0;
+    for (uint64_t k = 0; k < count; k++) r1cs::row_term(x, load_fp(z + (uint64_t)col[k] * 6), code[k], reinterpret_cast<const Fp*>(table));
+    const Fp r = r1cs::redc14(x);
+    memcpy(out, r.l, 48);
 }
 }

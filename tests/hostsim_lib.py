@@ -146,3 +146,86 @@ def r1cs_check(mats, witness, instance=None):
     fn = load().hostsim_r1cs_check
     fn.restype = ctypes.c_int64
     return fn(ctypes.c_uint64(mats["n_constraints"]), rp, col, val, witness.ctypes.data_as(u64p), ctypes.c_uint64(witness.shape[0]))
+
+
+def _limbs(v):
+    """a non-negative integer below 2^384 -> [6] uint64"""
+    return np.frombuffer(int(v).to_bytes(48, "little"), dtype=np.uint64).copy()
+
+
+def _int(a):
+    return int.from_bytes(np.ascontiguousarray(a, dtype=np.uint64).tobytes(), "little")
+
+
+def r1cs_encode(mats):
+    """the device evaluator's host encoder (csrc/r1cs_encode.hpp) on a matrices()-shaped dict -> (rc, enc); rc as blsw_r1cs_device_bytes, enc (rc == 0) =
+    dict(codes = [3] uint32 [nnz] (class << 30 | payload), table uint64 [size, 6] (class GEN's Montgomery coefficients), blk = block starts uint64
+    [n_blocks + 1], bytes = the device encoding's size)"""
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    nnz = np.array([mats[k][1].shape[0] for k in "ABC"], dtype=np.uint64)
+    rp = (u64p * 3)(*[mats[k][0].ctypes.data_as(u64p) for k in "ABC"])
+    col = (u32p * 3)(*[mats[k][1].ctypes.data_as(u32p) for k in "ABC"])
+    val = (u64p * 3)(*[mats[k][2].ctypes.data_as(u64p) for k in "ABC"])
+    codes = [np.zeros(max(1, int(n)), dtype=np.uint32) for n in nnz]
+    cp = (u32p * 3)(*[c.ctypes.data_as(u32p) for c in codes])
+    table = np.zeros((max(1, int(nnz.sum())), 6), dtype=np.uint64)
+    blk = np.zeros(mats["n_constraints"] + 1, dtype=np.uint64)
+    size, n_blk, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load().hostsim_r1cs_encode(ctypes.c_uint64(mats["n_constraints"]), ctypes.c_uint64(mats["n_instance_vars"]), ctypes.c_uint64(mats["n_witness"]),
+                                    nnz.ctypes.data_as(u64p), rp, col, val, cp, table.ctypes.data_as(u64p), ctypes.byref(size), blk.ctypes.data_as(u64p),
+                                    ctypes.byref(n_blk), ctypes.byref(nbytes))
+    if rc:
+        return rc, None
+    return 0, {"codes": [c[:int(n)] for c, n in zip(codes, nnz)], "table": table[:size.value].copy(), "blk": blk[:n_blk.value + 1].copy(), "bytes": nbytes.value}
+
+
+def r1cs_row(col, code, table, z):
+    """REDC(<row, z>) by the kernel's row functions (csrc/r1cs_row.hpp) on the host: the row's columns and entry codes, the encoder's table, z uint64
+    [n_z, 6] stored integers -> the reduced row value as an integer"""
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    col = np.ascontiguousarray(col, dtype=np.uint32)
+    code = np.ascontiguousarray(code, dtype=np.uint32)
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    assert z.dtype == np.uint64 and z.flags.c_contiguous and col.shape == code.shape and (col.size == 0 or int(col.max()) < z.shape[0])
+    gen = (code >> 30) == 2
+    assert not gen.any() or int((code[gen] & 0x3FFFFFFF).max()) < table.shape[0]
+    out = np.zeros(6, dtype=np.uint64)
+    fn = load().hostsim_r1cs_row
+    fn.restype = None
+    fn(col.ctypes.data_as(u32p), code.ctypes.data_as(u32p), ctypes.c_uint64(col.size), table.ctypes.data_as(u64p), z.ctypes.data_as(u64p), out.ctypes.data_as(u64p))
+    return _int(out)
+
+
+def _fp_binary(name, a, b):
+    a, b, r = _limbs(a), _limbs(b), np.zeros(6, dtype=np.uint64)
+    fn = getattr(load(), name)
+    fn.restype = None
+    fn(a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), r.ctypes.data_as(u64p))
+    return _int(r)
+
+
+def _fp_unary(name, a):
+    a, r = _limbs(a), np.zeros(6, dtype=np.uint64)
+    fn = getattr(load(), name)
+    fn.restype = None
+    fn(a.ctypes.data_as(u64p), r.ctypes.data_as(u64p))
+    return _int(r)
+
+
+def fp_mul(a, b):
+    """fp.hpp's fp_mul (the 28-bit-limb product) on stored integers: a b R^-1 mod p"""
+    return _fp_binary("hostsim_fp_mul", a, b)
+
+
+def fp_mul32(a, b):
+    """fp.hpp's fp_mul32 (the 12 x 32-bit CIOS): a b R^-1 mod p"""
+    return _fp_binary("hostsim_fp_mul32", a, b)
+
+
+def fp_inv(a):
+    """fp.hpp's fp_inv (safegcd) on a stored Montgomery integer a = v R: v^-1 R mod p (0 for 0)"""
+    return _fp_unary("hostsim_fp_inv", a)
+
+
+def fp_inv_fermat(a):
+    return _fp_unary("hostsim_fp_inv_fermat", a)
