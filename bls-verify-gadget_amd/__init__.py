@@ -29,7 +29,7 @@ class blsw_layout_t(ctypes.Structure):
 
 
 class blsw_engine_options_t(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode msg_mode agg_inputs".split()]
+    _fields_ = [("device", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in "n_keys pairing_mode g2_mode expand_variant expand_store prio_mode place_lds consumer_mode output_form chain_variant n_pairs cofactor_mode params_mode group_ramp latency_mode pk_mode sig_mode msg_mode agg_inputs shared_keys".split()]
 
 
 class blsw_matrices_info_t(ctypes.Structure):
@@ -146,6 +146,14 @@ def lib():
         L.blsw_compact_locate.argtypes = [cl, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u32)]
         L.blsw_r1cs_check_compact.argtypes = [vp, cl, vp, vp, u64, vp, vp, vp]
         L.blsw_r1cs_evaluate_compact.argtypes = [vp, cl, vp, vp, u64, u64, u64, vp, vp, vp, vp]
+        L.blsw_keyset_bytes.argtypes = [u32, ctypes.POINTER(u64)]
+        L.blsw_keyset_create.argtypes = [ctypes.POINTER(vp), vp, u32, u32, ctypes.c_int32, vp, u64, vp]
+        L.blsw_keyset_table.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64)]
+        L.blsw_keyset_destroy.argtypes = [vp]
+        L.blsw_keyset_broadcast_rate.argtypes = [vp, vp, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_double)]
+        L.blsw_engine_submit_aggregate_keyset.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+        L.blsw_engine_submit_aggregate_keyset_compact.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.blsw_engine_expand_compact_keyset.argtypes = [vp, vp, vp, vp, u64, vp]
         _lib = L
     return _lib
 
@@ -159,7 +167,9 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate", "blsw_layout_inputs",
                     "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs", "blsw_layout_aggregate_inputs", "blsw_matrices_info_aggregate_inputs",
                     "blsw_matrices_fill_aggregate_inputs", "blsw_engine_submit_aggregate_io", "blsw_compact_layout", "blsw_compact_locate",
-                    "blsw_r1cs_check_compact", "blsw_r1cs_evaluate_compact"]
+                    "blsw_r1cs_check_compact", "blsw_r1cs_evaluate_compact", "blsw_keyset_bytes", "blsw_keyset_create", "blsw_keyset_table", "blsw_keyset_destroy",
+                    "blsw_keyset_broadcast_rate", "blsw_engine_submit_aggregate_keyset", "blsw_engine_submit_aggregate_keyset_compact",
+                    "blsw_engine_expand_compact_keyset"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -294,6 +304,62 @@ def compact_locate_all(layout, lane):
     return region, off, bit
 
 
+SEG_PK_ALLOC = 1942  # witnesses of one G1Var::new_variable(Witness): a key's block of the keys segment and of a KeySet's table
+
+
+def keyset_bytes(n_keys):
+    b = ctypes.c_uint64(0)
+    rc = lib().blsw_keyset_bytes(n_keys, ctypes.byref(b))
+    if rc:
+        raise BlswError("blsw_keyset_bytes failed: %d" % rc)
+    return b.value
+
+
+class KeySet:
+    """A key set shared by many aggregate_verify instances (blsw_keyset_*): pks_xy [K, 12] int64 affine Montgomery, (0, 0) = the point at infinity.
+    Its keys' allocation witnesses are computed once, on the current stream of `device`; a WitnessEngine(..., n_keys=K, shared_keys=1) of the same
+    output_form copies them into every instance's vector (submit_aggregate_keyset). .table: [K * 1942, 6] int64 view of the table."""
+
+    def __init__(self, pks_xy, device=None, output_form=0):
+        torch = _require_cuda()
+        assert pks_xy.dim() == 2 and pks_xy.shape[1] == 12 and pks_xy.shape[0] >= 1
+        self.device = torch.device(device if device is not None else (pks_xy.device if pks_xy.is_cuda else "cuda:%d" % torch.cuda.current_device()))
+        self.pks_xy = pks_xy.to(self.device).contiguous()
+        self.n_keys, self.output_form = int(pks_xy.shape[0]), int(output_form)
+        self.buffer = torch.empty(keyset_bytes(self.n_keys), dtype=torch.uint8, device=self.device)  # the allocator's blocks are 512-byte aligned
+        self._ks = ctypes.c_void_p()
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        rc = lib().blsw_keyset_create(ctypes.byref(self._ks), self.pks_xy.data_ptr(), self.n_keys, self.output_form, index, self.buffer.data_ptr(), self.buffer.numel(),
+                                      torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            self._ks = None
+            raise BlswError("blsw_keyset_create failed: %d" % rc)
+        ptr, n_el = ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = lib().blsw_keyset_table(self._ks, ctypes.byref(ptr), ctypes.byref(n_el))
+        if rc or ptr.value != self.buffer.data_ptr() or n_el.value != self.n_keys * SEG_PK_ALLOC:
+            raise BlswError("blsw_keyset_table failed: %d" % rc)
+        self.table = self.buffer[:n_el.value * FP_BYTES].view(torch.int64).view(n_el.value, 6)
+
+    def broadcast_rate(self, witness, order=0, reps=3):
+        """blsw_keyset_broadcast_rate: bytes per second the table is written into the heads of `witness` [n, stride, 6] at (order 0: what the engine launches)"""
+        r = ctypes.c_double(0)
+        rc = lib().blsw_keyset_broadcast_rate(self._ks, witness.data_ptr(), witness.shape[1], witness.shape[0], order, reps, ctypes.byref(r))
+        if rc:
+            raise BlswError("blsw_keyset_broadcast_rate failed: %d" % rc)
+        return r.value
+
+    def close(self):
+        if getattr(self, "_ks", None):
+            lib().blsw_keyset_destroy(self._ks)
+            self._ks = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class WitnessEngine:
     """Thin wrapper of blsw_engine_*: submit batches, flush, read results. max_steps batches are fused per launch group.
     Streaming consumers use the step numbers returned by submit(): wait_step(seq) / output_consumed(tensor)."""
@@ -314,6 +380,7 @@ class WitnessEngine:
         self.n_pairs = int(opt.n_pairs) if opt.n_pairs > 1 else 1
         self.msg_mode = int(opt.msg_mode)
         self.agg_inputs = int(opt.agg_inputs)
+        self.shared_keys = int(opt.shared_keys)
         self.layout = layout_aggregate(msg_len, self.n_keys, self.agg_inputs) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else
                                                                                   layout(msg_len, int(opt.params_mode), int(opt.pk_mode), int(opt.sig_mode), self.msg_mode))
         self.n_witness = self.layout["n_witness"]
@@ -456,6 +523,46 @@ class WitnessEngine:
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq
 
+    def _keyset_step(self, keyset, bitmap, sig_xy, msg):
+        K = self.n_keys
+        assert isinstance(keyset, KeySet) and K and bitmap.shape == (self.n, K) and sig_xy.shape == (self.n, 24) and msg.shape == (self.n, self.msg_len)
+        assert bitmap.is_contiguous() and sig_xy.is_contiguous() and msg.is_contiguous()
+
+    def submit_aggregate_keyset(self, keyset, bitmap, sig_xy, msg, witness=None, result=None, count=None, stream=None, instance=None):
+        """submit_aggregate of an engine created with shared_keys=1: the step's keys are `keyset` (a KeySet of this engine's n_keys, output_form and
+        device; the steps of one launch group may name different sets) -> step number. The vectors are those of submit_aggregate with the keys
+        replicated [n, K, 12]. The set's table must be complete on, or ordered before, the submitting stream."""
+        self._keyset_step(keyset, bitmap, sig_xy, msg)
+        if witness is not None:
+            assert witness.is_contiguous() and witness.shape[0] == self.n and witness.shape[1] >= self.n_witness
+        if instance is not None:
+            assert instance.is_contiguous() and tuple(instance.shape) == (self.n, self.n_instance_vars, 6)
+        seq = self.submitted()
+        rc = lib().blsw_engine_submit_aggregate_keyset(self._e, keyset._ks, bitmap.data_ptr(), sig_xy.data_ptr(), msg.data_ptr() if self.msg_len else None,
+                                                       instance.data_ptr() if instance is not None else None, witness.data_ptr() if witness is not None else None,
+                                                       witness.shape[1] if witness is not None else 0, result.data_ptr() if result is not None else None,
+                                                       count.data_ptr() if count is not None else None, self._stream(stream))
+        if rc:
+            raise (BlswBusy if rc == ERR_BUSY else BlswError)("blsw_engine_submit_aggregate_keyset failed: %d" % rc)
+        self._keep.append((keyset, bitmap, sig_xy, msg, witness, result, count, instance))
+        self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
+        return seq
+
+    def submit_aggregate_keyset_compact(self, keyset, bitmap, sig_xy, msg, compact, result=None, count=None, stream=None):
+        """submit_aggregate_keyset with the step's compact wire form in `compact` as its output (no key rows: the receiver's expand_compact takes
+        the set) -> step number"""
+        self._keyset_step(keyset, bitmap, sig_xy, msg)
+        assert compact.is_cuda and compact.is_contiguous() and compact.dtype.itemsize == 1 and compact.numel() >= self.compact_bytes()
+        seq = self.submitted()
+        rc = lib().blsw_engine_submit_aggregate_keyset_compact(self._e, keyset._ks, bitmap.data_ptr(), sig_xy.data_ptr(), msg.data_ptr() if self.msg_len else None,
+                                                               compact.data_ptr(), result.data_ptr() if result is not None else None,
+                                                               count.data_ptr() if count is not None else None, self._stream(stream))
+        if rc:
+            raise (BlswBusy if rc == ERR_BUSY else BlswError)("blsw_engine_submit_aggregate_keyset_compact failed: %d" % rc)
+        self._keep.append((keyset, bitmap, sig_xy, msg, compact, result, count))
+        self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
+        return seq
+
     def compact_bytes(self):
         """Bytes of one batch in compact wire form (bit-packed SHA witnesses + staged field witnesses, ~2.6 MB per instance)."""
         return self._counter(lib().blsw_engine_compact_bytes)
@@ -499,11 +606,15 @@ class WitnessEngine:
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq
 
-    def expand_compact(self, compact, witness, stream=None):
-        """Receiver side: one batch in compact form (this engine's or another rank's) -> its n witness vectors in `witness`."""
+    def expand_compact(self, compact, witness, stream=None, keyset=None):
+        """Receiver side: one batch in compact form (this engine's or another rank's) -> its n witness vectors in `witness`.
+        keyset: the step's KeySet (engines with shared_keys=1: the compact form carries no key rows)."""
         assert compact.is_cuda and compact.is_contiguous() and compact.numel() >= self.compact_bytes()
         assert witness.is_contiguous() and witness.shape[0] == self.n and witness.shape[1] >= self.n_witness
-        rc = lib().blsw_engine_expand_compact(self._e, compact.data_ptr(), witness.data_ptr(), witness.shape[1], self._stream(stream))
+        if keyset is not None:
+            rc = lib().blsw_engine_expand_compact_keyset(self._e, keyset._ks, compact.data_ptr(), witness.data_ptr(), witness.shape[1], self._stream(stream))
+        else:
+            rc = lib().blsw_engine_expand_compact(self._e, compact.data_ptr(), witness.data_ptr(), witness.shape[1], self._stream(stream))
         if rc:
             raise BlswError("blsw_engine_expand_compact failed: %d" % rc)
 
@@ -847,11 +958,33 @@ def aggregate_verify(parameters, public_keys, bitmap, message, signature, want_w
     bitmap [n, K] uint8 (0/1) or a Boolean vector, message [n, msg_len] uint8 or a UInt8 vector, signature.xy [n, 24].
     Returns (result int32 [n], count int32 [n], witness). With an argument allocated as Input (PublicKeyVar.new_input, Boolean.new_input,
     UInt8.new_input_vec, SignatureVar.new_input) the circuit is the one of layout_aggregate(msg_len, K, mask): a direct-mode engine runs it and
-    the call returns (result, count, witness, instance) with instance [n, n_instance_vars, 6] = every instance's instance_assignment."""
+    the call returns (result, count, witness, instance) with instance [n, n_instance_vars, 6] = every instance's instance_assignment.
+    public_keys may be a KeySet (its K keys allocated as witnesses once, the same committee for every instance): the same circuit and vectors as
+    with the keys replicated [n, K, 12], through a direct-mode engine with shared_keys; the return value follows the other arguments' modes."""
     torch = _require_cuda()
     assert isinstance(parameters, ParametersVar)
     bit_var = bitmap if isinstance(bitmap, Boolean) else Boolean(bitmap)
     msg_var = message if isinstance(message, UInt8) else UInt8(message)
+    if isinstance(public_keys, KeySet):
+        if parameters.mode != "Constant":
+            raise BlswError("aggregate_verify with a KeySet: ParametersVar allocated as %s is not offered (Constant)" % parameters.mode)
+        mask = ((AGG_BITMAP_INPUT if bit_var.mode == "Input" else 0) | (AGG_MSG_INPUT if msg_var.mode == "Input" else 0) | (AGG_SIG_INPUT if signature.mode == "Input" else 0))
+        sig, bits, msg = signature.xy.contiguous(), bit_var.bits.contiguous(), msg_var.bytes.contiguous()
+        n, K, msg_len = bits.shape[0], public_keys.n_keys, msg.shape[1]
+        lay = layout_aggregate(msg_len, K, mask)
+        eng = WitnessEngine(n, msg_len, max_steps=1, n_buffers=1, device=public_keys.device, reserve_bytes=n * lay["n_witness"] * 48 if want_witness else 0, n_keys=K,
+                            agg_inputs=mask, shared_keys=1, output_form=public_keys.output_form)
+        try:
+            res = torch.empty(n, dtype=torch.int32, device=eng.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=eng.device)
+            wit = eng.new_witness_tensor() if want_witness else None
+            inst = eng.new_instance_tensor() if mask else None
+            eng.submit_aggregate_keyset(public_keys, bits, sig, msg, witness=wit, result=res, count=cnt, instance=inst)
+            eng.flush()
+            torch.cuda.synchronize(eng.device)
+        finally:
+            eng.close()
+        return (res, cnt, wit, inst) if mask else (res, cnt, wit)
     mask = ((AGG_KEYS_INPUT if public_keys.mode == "Input" else 0) | (AGG_BITMAP_INPUT if bit_var.mode == "Input" else 0) |
             (AGG_MSG_INPUT if msg_var.mode == "Input" else 0) | (AGG_SIG_INPUT if signature.mode == "Input" else 0))
     pks, sig, bitmap, message = public_keys.xy.contiguous(), signature.xy.contiguous(), bit_var.bits.contiguous(), msg_var.bytes.contiguous()

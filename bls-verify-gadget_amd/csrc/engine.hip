@@ -106,10 +106,22 @@ struct GroupTrace {
     uint64_t lanes;
     bool lat;
 };
+struct blsw_keyset {
+    uint32_t n_keys = 0, form = 0;
+    int device = -1;
+    Fp* table = nullptr;  // [n_keys * SEG_PK_ALLOC] in `form`
+    Fp* proj = nullptr;   // [3][n_keys] Montgomery
+};
 struct blsw_engine {
     uint64_t n = 0;
     uint32_t msg_len = 0, max_steps = 0;
     blsw_layout_t L, LS;
+    // options.shared_keys: the first `head` elements of every vector (the keys segment, off_keys == 0) are a copy of the step's key set and exist
+    // nowhere in the engine. LR is the layout of the ROWS the engine computes, stages and places — the same circuit with its keys segment cut out,
+    // which is field for field the Keys-Input layout — against an output advanced by `head` elements; L (the layout the caller sees, all-Witness
+    // keys) stays what the kernels take their direct-mode offsets and their instance-variable rules from. head == 0: LR == L.
+    blsw_layout_t LR;
+    uint32_t head = 0;
     Modes modes = DEFAULT_MODES;
     blsw_engine_options_t opt;
     int device = -1;
@@ -174,12 +186,13 @@ static void engine_free(blsw_engine* e) {
 // field witnesses of one step: staged rows (lanes first .. first + n of the tiles at `staging` / the rows at `pair`) -> their
 // places around the SHA segment of the step's witness vectors
 static void launch_place(blsw_engine* e, hipStream_t st, const Fp* staging, const Fp* pair, uint32_t split_row, uint64_t first, uint64_t* out, uint64_t out_stride) {
-    const uint32_t rows = e->L.n_witness - e->L.sha_bits;
+    const blsw_layout_t& R = e->LR;  // the rows behind a shared head, placed against the output advanced by the head
+    const uint32_t rows = R.n_witness - R.sha_bits;
     const unsigned chunks = (rows * 3 + 256 * BLSW_PLACE_ITERS - 1) / (256 * BLSW_PLACE_ITERS);
     dim3 grid2(8 * ((chunks + 7) / 8) * (unsigned)e->n);
-    const MovedSegment mv = moved_segment(e->L, e->modes);
-    hipLaunchKernelGGL(k_place_field, grid2, dim3(256), 0, st, staging, pair, first, e->L.off_expand, e->L.sha_bits, rows, split_row, out, out_stride, (uint32_t)e->n,
-                       mv.lo, mv.len, mv.at);
+    const MovedSegment mv = moved_segment(R, e->modes);
+    hipLaunchKernelGGL(k_place_field, grid2, dim3(256), 0, st, staging, pair, first, R.off_expand, R.sha_bits, rows, split_row, out + (uint64_t)e->head * 6, out_stride,
+                       (uint32_t)e->n, mv.lo, mv.len, mv.at);
 }
 // N+1-pair product: a step's pair tiles, instance tiles and instance-major rows -> their places in the n instance vectors. Sources: the
 // group workspace (first lanes of the step given) or a compact buffer (first lanes 0, instance tiles tile_w wide)
@@ -212,8 +225,10 @@ static void launch_place_multi(blsw_engine* e, hipStream_t st, const Workspace& 
     hipLaunchKernelGGL(k_place_rows, dim3(chunks, n), dim3(256), 0, st, rows, ws.pair_rows, L.off_miller, out, out_stride);
 }
 static void launch_canonical(blsw_engine* e, hipStream_t st, uint64_t* out, uint64_t out_stride) {
-    const uint32_t K = e->L.n_pairs, rows = e->L.n_witness - K * e->L.sha_bits;
-    hipLaunchKernelGGL(k_canonical_rows, dim3((rows + 255) / 256, (unsigned)e->n), dim3(256), 0, st, out, out_stride, e->L.off_expand, e->L.sha_bits, rows, K, e->L.stride_hash);
+    const blsw_layout_t& R = e->LR;  // a shared head is a copy of a table that is in the output form already
+    const uint32_t K = R.n_pairs, rows = R.n_witness - K * R.sha_bits;
+    hipLaunchKernelGGL(k_canonical_rows, dim3((rows + 255) / 256, (unsigned)e->n), dim3(256), 0, st, out + (uint64_t)e->head * 6, out_stride, R.off_expand, R.sha_bits, rows, K,
+                       R.stride_hash);
 }
 // bit expansion in the engine's variant (options.expand_variant / expand_store / place_lds)
 static void engine_expand(const blsw_engine* e, hipStream_t st, const ExpandArgs& xa, unsigned n_y) {
@@ -281,6 +296,10 @@ static void materialise(blsw_engine* e, int k, uint32_t s) {
             hipEventRecord(e->ev_exp[2 * e->n_timed + 1], e->expand);
             e->n_timed++;
         }
+        // options.shared_keys: the head of every vector is the step's key table. With the expansion — the other kernel that needs nothing but the
+        // step's inputs — and behind the same waits: the output's release, and in consumer mode the hold-back of pump(). (Direct mode too: the
+        // expansion stream has waited for ev_sha, which follows the chains' own wait for the output's release in launch_group.)
+        if (e->head) launch_keys_broadcast(d.ks_table, e->head, d.out, d.out_stride, e->n, 0, e->expand);
     }
     hipEventRecord(b.ev_x[s], e->expand);
     hipStreamWaitEvent(e->place, b.ev_chains, 0);
@@ -388,6 +407,13 @@ static void options_layout(uint32_t msg_len, const blsw_engine_options_t* o, bls
     else
         make_layout(msg_len, L, 0, o->n_pairs > 1 ? o->n_pairs : 1, o->params_mode == 1, o->pk_mode == 1, o->sig_mode == 1, o->msg_mode == 1);
 }
+// the layout of the rows such an engine computes itself (blsw_engine::LR): with options.shared_keys the circuit's layout without its keys segment
+static void options_layout_rows(uint32_t msg_len, const blsw_engine_options_t* o, blsw_layout_t* L) {
+    if (o->shared_keys)
+        make_layout_aggregate(msg_len, L, o->n_keys, o->agg_inputs | BLSW_AGG_KEYS_INPUT);
+    else
+        options_layout(msg_len, o, L);
+}
 // is the message allocated with UInt8::new_input_vec?
 static bool options_msg_input(const blsw_engine_options_t* o) { return o->n_keys ? (o->agg_inputs & BLSW_AGG_MSG_INPUT) != 0 : o->msg_mode == 1; }
 
@@ -397,7 +423,7 @@ static int launch_group(blsw_engine* e) {
     if (steps == 0) return BLSW_OK;
     const uint32_t K = e->L.n_pairs;  // (pk, msg) pairs per instance: 1 except for the N+1-pair product
     // per-pair view: one lane per (instance, pair)
-    Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->L, e->staged, e->modes, (uint64_t)steps * e->n));
+    Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->LR, e->staged, e->modes, (uint64_t)steps * e->n));
     g.LS = e->LS;
     const bool msg_input = options_msg_input(&e->opt);
     if (msg_input) g.msg_wit_len = 0;  // UInt8::new_input_vec: k_msg_input writes the message segment, k_sha no message booleans
@@ -475,7 +501,9 @@ static int launch_group(blsw_engine* e) {
     // only the end of the group waits for (ev_side): the longest aux kernel no longer delays the pairing of a latency-bound group
     hipStream_t sb = b.st[1];
     launch_prepare(ck, vf, gs, 1, sb);
-    if (e->L.n_keys && e->L.pk_mode) {  // aggregate_verify with the keys as public inputs: nothing allocates them
+    if (e->head) {  // aggregate_verify with a shared key set per step: allocated once (blsw_keyset_create), read by every lane
+        hipLaunchKernelGGL(ck.agg_sum_ks, dim3(g1), dim3(64), 0, sb, g);
+    } else if (e->L.n_keys && e->L.pk_mode) {  // aggregate_verify with the keys as public inputs: nothing allocates them
         hipLaunchKernelGGL(ck.agg_sum_in, dim3(g1), dim3(64), 0, sb, g);
     } else if (e->L.n_keys) {  // aggregate_verify: one lane per (instance, key) allocates, then mapped_aggregate + pk != 0 + prepare_g1 per instance
         hipLaunchKernelGGL(ck.agg_keys, dim3((unsigned)((g.N * e->L.n_keys + 63) / 64)), dim3(64), 0, sb, g, g.ws.keyproj);
@@ -590,6 +618,8 @@ static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint3
     if (o->msg_mode > 1 || (o->msg_mode && (o->n_keys || o->n_pairs > 1 || o->params_mode || o->g2_mode))) return BLSW_ERR_ARG;
     // the aggregate circuit's own allocation modes (BLSW_AGG_*_INPUT): an aggregate engine only
     if (o->agg_inputs > 15 || (o->agg_inputs && !o->n_keys)) return BLSW_ERR_ARG;
+    // a shared key set per step: an aggregate engine whose keys are allocated as witnesses
+    if (o->shared_keys > 1 || (o->shared_keys && (!o->n_keys || (o->agg_inputs & BLSW_AGG_KEYS_INPUT)))) return BLSW_ERR_ARG;
     return BLSW_OK;
 }
 
@@ -643,6 +673,7 @@ int blsw_engine_options_default(blsw_engine_options_t* o) {
     o->sig_mode = 0;
     o->msg_mode = 0;
     o->agg_inputs = 0;
+    o->shared_keys = 0;
     return BLSW_OK;
 }
 
@@ -651,7 +682,7 @@ int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_st
     if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
     blsw_layout_t L;
     const uint32_t K = options->n_pairs > 1 ? options->n_pairs : 1;
-    options_layout(msg_len, options, &L);
+    options_layout_rows(msg_len, options, &L);
     const bool staged = max_steps > 1 || n_buffers > 1;
     // the same workspace serves every kernel variant: the largest carve of the three mode combinations
     uint64_t need = 0;
@@ -719,7 +750,9 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     e->cofactor_mode = options->cofactor_mode;
     e->chains_inlined = options->chain_variant == 2 || (options->chain_variant == 0 && !e->staged);
     options_layout(msg_len, options, &e->L);
-    e->LS = e->L.n_pairs > 1 ? staging_layout_multi(e->L).LS : staging_layout(e->L, e->modes);
+    options_layout_rows(msg_len, options, &e->LR);
+    e->head = options->shared_keys ? options->n_keys * SEG_PK_ALLOC : 0;
+    e->LS = e->L.n_pairs > 1 ? staging_layout_multi(e->L).LS : staging_layout(e->LR, e->modes);
     for (int i = 0; i < BLSW_MAX_CONSUMED; i++) {
         e->consumed_ptr[i] = nullptr;
         e->consumed_ev[i] = nullptr;
@@ -891,7 +924,7 @@ int blsw_engine_submit_bytes(blsw_engine_t* e, const uint8_t* d_pk48, const uint
 // aggregate_verify through the engine (an engine created with options.n_keys = K): one batch of n instances of K keys each
 int blsw_engine_submit_aggregate(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
                                  uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream_) {
-    if (!e || !e->L.n_keys || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    if (!e || !e->L.n_keys || e->head || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
     StepDesc d = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, d_pks_xy, d_bitmap, d_count, nullptr};
     return engine_submit(e, d, stream_);
 }
@@ -899,8 +932,19 @@ int blsw_engine_submit_aggregate(blsw_engine_t* e, const uint64_t* d_pks_xy, con
 // the same step with its instance_assignment (every aggregate engine; options.agg_inputs says which arguments are public inputs)
 int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
                                     uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream_) {
-    if (!e || !e->L.n_keys || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    if (!e || !e->L.n_keys || e->head || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
     StepDesc d = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, d_pks_xy, d_bitmap, d_count, nullptr, nullptr, d_instance};
+    return engine_submit(e, d, stream_);
+}
+// the step's keys as a shared key set (an engine with options.shared_keys)
+static bool keyset_fits(const blsw_engine* e, const blsw_keyset* ks) {
+    return e && e->head && ks && ks->n_keys == e->L.n_keys && ks->form == e->opt.output_form && ks->device == e->device;
+}
+int blsw_engine_submit_aggregate_keyset(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                        uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream_) {
+    if (!keyset_fits(e, ks) || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    StepDesc d = {nullptr, d_sig_xy, d_msg, d_witness, witness_stride, d_result, nullptr, d_bitmap, d_count, nullptr, nullptr, d_instance,
+                  reinterpret_cast<const uint64_t*>(ks->table), ks->proj};
     return engine_submit(e, d, stream_);
 }
 
@@ -908,12 +952,12 @@ int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, 
 // rate; 2.6 MB per instance travel instead of 34 MB and the receiver expands them).
 int blsw_engine_compact_bytes(blsw_engine_t* e, uint64_t* bytes) {
     if (!e || !bytes || !e->staged || !compact_shape_ok(e->n, e->L.n_pairs)) return BLSW_ERR_ARG;
-    *bytes = compact_form(e->n, carve(nullptr, e->n * e->L.n_pairs, e->L, true, e->modes, e->n), e->L.n_pairs).total;
+    *bytes = compact_form(e->n, carve(nullptr, e->n * e->L.n_pairs, e->LR, true, e->modes, e->n), e->L.n_pairs).total;
     return BLSW_OK;
 }
 // the compact steps of a staged engine of these arguments, described for a consumer (blsw_r1cs_check_compact); host only
 int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, blsw_compact_layout_t* out) {
-    if (!out || !options || n % 64 || options->n_pairs > 1) return BLSW_ERR_ARG;
+    if (!out || !options || n % 64 || options->n_pairs > 1 || options->shared_keys) return BLSW_ERR_ARG;
     if (int rc = check_options(n, msg_len, 2, 1, options)) return rc;  // any staged engine: the step's form does not depend on max_steps / n_buffers
     blsw_layout_t L;
     options_layout(msg_len, options, &L);
@@ -933,8 +977,15 @@ int blsw_engine_submit_compact(blsw_engine_t* e, const uint64_t* d_pk_xy, const 
 }
 int blsw_engine_submit_aggregate_compact(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
                                          void* d_compact, int32_t* d_result, uint32_t* d_count, void* stream_) {
-    if (!e || !e->L.n_keys || !e->staged || e->n % 64 || !d_compact || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    if (!e || !e->L.n_keys || e->head || !e->staged || e->n % 64 || !d_compact || !d_pks_xy || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
     StepDesc d = {nullptr, d_sig_xy, d_msg, nullptr, 0, d_result, d_pks_xy, d_bitmap, d_count, d_compact};
+    return engine_submit(e, d, stream_);
+}
+int blsw_engine_submit_aggregate_keyset_compact(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                                void* d_compact, int32_t* d_result, uint32_t* d_count, void* stream_) {
+    if (!keyset_fits(e, ks) || !e->staged || e->n % 64 || !d_compact || !d_bitmap || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;
+    StepDesc d = {nullptr, d_sig_xy, d_msg, nullptr, 0, d_result, nullptr, d_bitmap, d_count, d_compact, nullptr, nullptr,
+                  reinterpret_cast<const uint64_t*>(ks->table), ks->proj};
     return engine_submit(e, d, stream_);
 }
 // the N+1-pair product's step in compact form (engine created with options.n_pairs = K; n K a multiple of 64, n a divisor or multiple of 64)
@@ -946,12 +997,13 @@ int blsw_engine_submit_multi_compact(blsw_engine_t* e, const uint64_t* d_pks_xy,
 }
 // receiver side: one batch in compact form -> its n witness vectors, on `stream` (the expansion and placement kernels of the
 // engine's own steps, pointed at the compact buffer)
-int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream_) {
+static int expand_compact(blsw_engine_t* e, const blsw_keyset* ks, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream_) {
     if (!e || !e->staged || !compact_shape_ok(e->n, e->L.n_pairs) || !d_compact || !d_witness || witness_stride < e->L.n_witness) return BLSW_ERR_ARG;
     DeviceGuard guard(e->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     const uint32_t K = e->L.n_pairs;
-    const Workspace w = carve(nullptr, e->n * K, e->L, true, e->modes, e->n);
+    const Workspace w = carve(nullptr, e->n * K, e->LR, true, e->modes, e->n);
+    if (ks) launch_keys_broadcast(reinterpret_cast<const uint64_t*>(ks->table), e->head, d_witness, witness_stride, e->n, 0, st);  // the head the form does not carry
     const CompactForm cf = compact_form(e->n, w, K);
     const char* src = reinterpret_cast<const char*>(d_compact);
     ExpandArgs xa = {reinterpret_cast<const uint32_t*>(src), w.sha_words, 0, e->L.sha_bits, e->L.off_expand, d_witness, witness_stride, K, K > 1 ? e->L.stride_hash : 0u, 0, (int)e->opt.output_form};
@@ -963,6 +1015,93 @@ int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t
         launch_place(e, st, reinterpret_cast<const Fp*>(src + cf.off_staging), reinterpret_cast<const Fp*>(src + cf.off_pair), w.split_row, 0, d_witness, witness_stride);
     if (e->opt.output_form) launch_canonical(e, st, d_witness, witness_stride);
     return hip_ok(hipGetLastError(), "expand compact");
+}
+int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream_) {
+    if (!e || e->head) return BLSW_ERR_ARG;  // a shared-keys step needs its key set: blsw_engine_expand_compact_keyset
+    return expand_compact(e, nullptr, d_compact, d_witness, witness_stride, stream_);
+}
+int blsw_engine_expand_compact_keyset(blsw_engine_t* e, const blsw_keyset_t* ks, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream_) {
+    if (!keyset_fits(e, ks)) return BLSW_ERR_ARG;
+    return expand_compact(e, ks, d_compact, d_witness, witness_stride, stream_);
+}
+
+// ---- shared key sets (include/blsw.h, ABI 15). The caller's buffer: the table, then the allocated projective keys, each 256-byte aligned
+static uint64_t keyset_offsets(uint32_t n_keys, uint64_t* off_proj) {
+    *off_proj = align_up((uint64_t)n_keys * SEG_PK_ALLOC * sizeof(Fp), 256);
+    return *off_proj + align_up(3ull * n_keys * sizeof(Fp), 256);
+}
+int blsw_keyset_bytes(uint32_t n_keys, uint64_t* bytes) {
+    if (!bytes || n_keys == 0 || n_keys > 65535) return BLSW_ERR_ARG;
+    uint64_t off_proj;
+    *bytes = keyset_offsets(n_keys, &off_proj);
+    return BLSW_OK;
+}
+int blsw_keyset_create(blsw_keyset_t** out, const uint64_t* d_pks_xy, uint32_t n_keys, uint32_t output_form, int32_t device, void* d_buffer, uint64_t buffer_bytes,
+                       void* stream_) {
+    uint64_t need = 0, off_proj = 0;
+    if (!out || !d_pks_xy || !d_buffer || output_form > 1 || blsw_keyset_bytes(n_keys, &need) || buffer_bytes < need || (reinterpret_cast<uintptr_t>(d_buffer) & 255))
+        return BLSW_ERR_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BLSW_ERR_NO_DEVICE;
+    int dev = device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return BLSW_ERR_NO_DEVICE;
+    if (dev >= ndev) return BLSW_ERR_ARG;
+    DeviceGuard guard(dev);
+    keyset_offsets(n_keys, &off_proj);
+    blsw_keyset* ks = new blsw_keyset();
+    ks->n_keys = n_keys;
+    ks->form = output_form;
+    ks->device = dev;
+    ks->table = reinterpret_cast<Fp*>(d_buffer);
+    ks->proj = reinterpret_cast<Fp*>(reinterpret_cast<char*>(d_buffer) + off_proj);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    launch_keyset_alloc(d_pks_xy, n_keys, ks->table, ks->proj, st);
+    if (output_form) {  // the table as canonical integers, in place (one vector of n_keys * SEG_PK_ALLOC rows and no SHA segment); the points stay Montgomery
+        const uint32_t rows = n_keys * SEG_PK_ALLOC;
+        hipLaunchKernelGGL(k_canonical_rows, dim3((rows + 255) / 256, 1), dim3(256), 0, st, reinterpret_cast<uint64_t*>(ks->table), 0, rows, 0u, rows, 1u, 0u);
+    }
+    if (hip_ok(hipGetLastError(), "keyset create")) {
+        delete ks;
+        return BLSW_ERR_HIP;
+    }
+    *out = ks;
+    return BLSW_OK;
+}
+int blsw_keyset_table(const blsw_keyset_t* ks, const uint64_t** d_table, uint64_t* n_elements) {
+    if (!ks || !d_table || !n_elements) return BLSW_ERR_ARG;
+    *d_table = reinterpret_cast<const uint64_t*>(ks->table);
+    *n_elements = (uint64_t)ks->n_keys * SEG_PK_ALLOC;
+    return BLSW_OK;
+}
+int blsw_keyset_destroy(blsw_keyset_t* ks) {
+    if (!ks) return BLSW_ERR_ARG;
+    delete ks;
+    return BLSW_OK;
+}
+int blsw_keyset_broadcast_rate(const blsw_keyset_t* ks, uint64_t* d_witness, uint64_t witness_stride, uint64_t n, uint32_t order, uint32_t reps, double* bytes_per_s) {
+    if (!ks || !d_witness || n == 0 || order > 1 || reps == 0 || !bytes_per_s || witness_stride < (uint64_t)ks->n_keys * SEG_PK_ALLOC) return BLSW_ERR_ARG;
+    DeviceGuard guard(ks->device);
+    const uint64_t elems = (uint64_t)ks->n_keys * SEG_PK_ALLOC;
+    const uint64_t* table = reinterpret_cast<const uint64_t*>(ks->table);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = hip_ok(hipEventCreate(&e0), "event create");
+    if (!rc) rc = hip_ok(hipEventCreate(&e1), "event create");
+    if (!rc) {
+        launch_keys_broadcast(table, elems, d_witness, witness_stride, n, order, 0);
+        hipEventRecord(e0, 0);
+        for (uint32_t r = 0; r < reps; r++) launch_keys_broadcast(table, elems, d_witness, witness_stride, n, order, 0);
+        hipEventRecord(e1, 0);
+        rc = hip_ok(hipEventSynchronize(e1), "event sync");
+    }
+    if (!rc) {
+        float ms = 0;
+        rc = hip_ok(hipEventElapsedTime(&ms, e0, e1), "event elapsed");
+        if (!rc) *bytes_per_s = (double)elems * sizeof(Fp) * n * reps / (ms * 1e-3);
+    }
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
 }
 
 // launches whatever is pending and makes `stream` wait for every group issued so far

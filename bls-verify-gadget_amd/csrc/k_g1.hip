@@ -107,5 +107,21 @@ __global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum_in)(Group
     KeyInputSrc<LdFpGlobal> src = {reinterpret_cast<const Fp*>(g.desc[id.s].keys + (uint64_t)id.i * nk * 12), LdFpGlobal()};
     agg_sum_lane(g, id, I, src, g.desc[id.s].bitmap + (uint64_t)id.i * nk);
 }
+// the same with the keys of the step's shared key set (options.shared_keys): K allocated projective points [3][K], the same for every lane of the
+// step — the address is wave-uniform wherever a wave lies within one step, and nothing of the keys is written by this engine
+struct KeySetSrc {
+    const Fp* p;
+    uint32_t K;
+    __device__ __forceinline__ Proj<OpsFp> ld(uint32_t k) const { return {ld_fp(p + k), ld_fp(p + K + k), ld_fp(p + 2 * (uint64_t)K + k)}; }
+};
+__global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_agg_sum_ks)(Group g) {
+    if (g.chain_prio) __builtin_amdgcn_s_setprio(3);
+    uint64_t I = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= g.N) return;
+    LaneId id = lane_id(g, I);
+    const uint32_t nk = g.L.n_keys;
+    KeySetSrc src = {g.desc[id.s].ks_proj, nk};
+    agg_sum_lane(g, id, I, src, g.desc[id.s].bitmap + (uint64_t)id.i * nk);
+}
 
 }  // namespace blsw

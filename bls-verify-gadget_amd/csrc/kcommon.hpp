@@ -215,6 +215,11 @@ struct StepDesc {
     const int32_t* status;
     // blsw_engine_submit_io: [n][n_instance_vars][6] instance_assignment of every instance (element 0 = one), or nullptr
     uint64_t* inst;
+    // blsw_engine_submit_aggregate_keyset (an engine with options.shared_keys): the step's key set — its table of allocation witnesses
+    // [n_keys * SEG_PK_ALLOC] elements in the engine's output form (host side: the source of the head broadcast) and its allocated projective keys
+    // [3][n_keys] (x, y, z rows, Montgomery), what k_agg_sum_ks reads in place of ws.keyproj
+    const uint64_t* ks_table;
+    const Fp* ks_proj;
 };
 __device__ __forceinline__ int32_t step_result(const StepDesc& d, uint32_t i, bool res) {
     if (d.status && (d.status[2 * i] | d.status[2 * i + 1])) return 0;
@@ -452,6 +457,7 @@ BLSW_CHAIN_I(k_g1, (Group g))
 BLSW_CHAIN_I(k_agg_keys, (Group g, Fp* keyproj))
 BLSW_CHAIN_I(k_agg_sum, (Group g, const Fp* keyproj))
 BLSW_CHAIN_I(k_agg_sum_in, (Group g))
+BLSW_CHAIN_I(k_agg_sum_ks, (Group g))
 BLSW_CHAIN_I(k_cofactor, (Group g))
 BLSW_CHAIN_I(k_cofactor_chunk, (Group g))
 BLSW_CHAIN_I(k_cofactor_join, (Group g))
@@ -550,6 +556,7 @@ struct ChainKernels {
     void (*agg_keys)(Group, Fp*);
     void (*agg_sum)(Group, const Fp*);
     void (*agg_sum_in)(Group);  // the keys are public inputs (L.pk_mode): no allocated keys to read
+    void (*agg_sum_ks)(Group);  // the keys are the step's shared key set (StepDesc::ks_proj)
     void (*cofactor)(Group);
     void (*cofactor_chunk)(Group);  // the cofactor segment with its three chunks on three lanes, and the join (cofactor_par.hpp)
     void (*cofactor_join)(Group);
@@ -569,7 +576,7 @@ inline ChainKernels chain_kernels(bool inlined, bool quad) {
 #define BLSW_PICK_I(name) (inlined ? name##_inl : name)
 #define BLSW_PICK_Q(name) (quad ? name##_q : name)
 #define BLSW_PICK_IQ(name) (quad ? name##_q : BLSW_PICK_I(name))
-    return {BLSW_PICK_I(k_sha), BLSW_PICK_I(k_g1), BLSW_PICK_I(k_agg_keys), BLSW_PICK_I(k_agg_sum), BLSW_PICK_I(k_agg_sum_in), BLSW_PICK_I(k_cofactor),
+    return {BLSW_PICK_I(k_sha), BLSW_PICK_I(k_g1), BLSW_PICK_I(k_agg_keys), BLSW_PICK_I(k_agg_sum), BLSW_PICK_I(k_agg_sum_in), BLSW_PICK_I(k_agg_sum_ks), BLSW_PICK_I(k_cofactor),
             BLSW_PICK_I(k_cofactor_chunk), BLSW_PICK_I(k_cofactor_join), BLSW_PICK_IQ(k_g2_alloc), BLSW_PICK_IQ(k_map), BLSW_PICK_IQ(k_prepare), BLSW_PICK_Q(k_prepv_chain),
             BLSW_PICK_Q(k_cofv_chain), BLSW_PICK_Q(k_cofv_bwd), BLSW_PICK_Q(k_cofv_acc), BLSW_PICK_Q(k_cofv_az), quad ? 4u : 1u};
 #undef BLSW_PICK_I
@@ -675,6 +682,10 @@ inline void launch_prepare(const ChainKernels& ck, bool vf, const Group& g, int 
 }
 inline void launch_g2_alloc(const ChainKernels& ck, const Group& g, hipStream_t st) { hipLaunchKernelGGL(ck.g2_alloc, dim3(item_grid(g.N, ck.lpi)), dim3(64), 0, st, g); }
 // host-side launch helpers that live next to their (templated) kernels
+// shared key sets (k_keyset.hip): the allocation chain of K keys into a dense table + their projective points [3][K]; the table copied into the
+// heads of n instance vectors (order: 0 instance fastest, 1 chunk fastest — blsw_keyset_broadcast_rate measures both, the engine launches 0)
+void launch_keyset_alloc(const uint64_t* pks_xy, uint32_t n_keys, Fp* table, Fp* proj, hipStream_t st);
+void launch_keys_broadcast(const uint64_t* table, uint64_t n_elements, uint64_t* d_witness, uint64_t stride, uint64_t n, uint32_t order, hipStream_t st);
 void launch_expand(uint32_t variant, uint32_t store, unsigned lds, hipStream_t st, ExpandArgs a, unsigned n_y);
 void launch_pairing(const Group& g, const Modes& m, hipStream_t st);
 #define BLSW_VLINE_ROWS (6u * 68u)  // vpairing.hpp: per G2 point, 68 steps x (c0, c1 x_P, c2 y_P), two Fp each

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 14
+#define BLSW_ABI_VERSION 15
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -213,6 +213,12 @@ typedef struct {
                               Witness. With BLSW_AGG_KEYS_INPUT nothing allocates keys: no allocation kernel runs and the workspace holds no projective keys.
                               blsw_engine_submit_aggregate_io also writes instance_assignment. The aggregate circuit's modes are this mask: pk_mode, sig_mode
                               and msg_mode stay refused together with n_keys. BLSW_ERR_ARG: a value above 15, a non-zero value with n_keys == 0. */
+    uint32_t shared_keys;  /* aggregate_verify engines (ABI 15): 0 (default) every step brings its keys [n][K][12] and allocates them per instance; 1 = every step
+                              names a key set (blsw_keyset_t below) whose allocation witnesses were computed once: they are copied into the head of every
+                              instance's vector and nothing of the keys is staged, kept in the workspace or carried by the compact form. The circuit, the
+                              layout (blsw_layout_aggregate_inputs of agg_inputs) and every output element are those of shared_keys 0. Batches go through
+                              blsw_engine_submit_aggregate_keyset / _keyset_compact. BLSW_ERR_ARG: a value above 1, n_keys == 0, agg_inputs with
+                              BLSW_AGG_KEYS_INPUT (Input keys have no allocation witnesses to share). */
 } blsw_engine_options_t;
 /* the defaults (pure: measurement scripts set the fields they want to vary). The one environment variable the library reads is the
  * diagnostic BLSW_TRACE_GROUP=1: an engine prints its launch groups' stage times to stderr at blsw_engine_destroy. */
@@ -351,6 +357,39 @@ int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_
  * that holds the bit (then *bit = its position in the word, LSB = 0) or of the element's 48 bytes (*bit = 0). The one statement of the rule:
  * the device checker evaluates the same function. BLSW_ERR_ARG: a NULL pointer, k or lane out of range, an inconsistent layout. Host only. */
 int blsw_compact_locate(const blsw_compact_layout_t* layout, uint32_t k, uint64_t lane, uint32_t* region, uint64_t* byte_offset, uint32_t* bit);
+/* ABI 15: a key set shared by many aggregate_verify instances (a committee that signs many messages: only bitmap, message and signature change).
+ * The allocation witnesses of its K keys — SEG 1 942 elements per key, G1Var::new_variable(Witness) with its in-circuit prime-order check, what
+ * blsw_engine_submit_aggregate computes per (instance, key) — are computed ONCE into a device table; an engine with options.shared_keys copies the
+ * table into elements [0, K * 1942) of every instance's vector (off_keys == 0) and reads the K allocated projective keys for mapped_aggregate.
+ * Conventions of blsw_r1cs_create: the caller owns d_buffer (256-byte aligned, blsw_keyset_bytes bytes), which must outlive the handle AND every step
+ * submitted with it; device -1 = the current device; create is asynchronous on `stream` (it copies nothing from the host) and every rule is checked on
+ * the host before any HIP call. A step that uses the set must be submitted on `stream`, or on a stream ordered behind the create.
+ *   d_pks_xy [K][12] u64 affine Montgomery, (0, 0) = the point at infinity;  output_form as blsw_engine_options_t.output_form: the table's element form
+ *   blsw_keyset_table: the table [K * 1942][6] u64 (key k at element k * 1942, allocation order) in that form
+ * BLSW_ERR_ARG: a NULL handle / key / buffer / output pointer, n_keys == 0 or above 65535, output_form > 1, a misaligned d_buffer, buffer_bytes below
+ * blsw_keyset_bytes. */
+typedef struct blsw_keyset blsw_keyset_t;
+int blsw_keyset_bytes(uint32_t n_keys, uint64_t* bytes);
+int blsw_keyset_create(blsw_keyset_t** out, const uint64_t* d_pks_xy, uint32_t n_keys, uint32_t output_form, int32_t device, void* d_buffer, uint64_t buffer_bytes,
+                       void* stream);
+int blsw_keyset_table(const blsw_keyset_t* ks, const uint64_t** d_table, uint64_t* n_elements);
+int blsw_keyset_destroy(blsw_keyset_t* ks);
+/* blsw_engine_submit_aggregate_io / _aggregate_compact / blsw_engine_expand_compact for an engine with options.shared_keys: the step's keys are `ks`
+ * (per STEP: the steps of one launch group may name different sets), everything else as there. d_instance may be NULL. The compact form carries no key
+ * rows (blsw_engine_compact_bytes is smaller by n * K * 1942 * 48 bytes): the receiver supplies the set when it expands. BLSW_ERR_ARG: an engine
+ * without shared_keys, a NULL set, a set whose n_keys, output_form or device differ from the engine's. The entry points that take d_pks_xy
+ * (blsw_engine_submit_aggregate, _io, _compact) and blsw_engine_expand_compact refuse an engine with shared_keys; blsw_compact_layout refuses the
+ * option (the compact checker has no head region yet). */
+int blsw_engine_submit_aggregate_keyset(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                        uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream);
+int blsw_engine_submit_aggregate_keyset_compact(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
+                                                void* d_compact, int32_t* d_result, uint32_t* d_count, void* stream);
+int blsw_engine_expand_compact_keyset(blsw_engine_t* e, const blsw_keyset_t* ks, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream);
+/* Same-box rate of the head broadcast alone (the kernel a shared_keys step runs beside its expansion): the set's table copied into the heads of
+ * d_witness [n][witness_stride] (overwritten; witness_stride >= K * 1942), `reps` passes after one warm-up pass on the NULL stream of the set's device;
+ * bytes WRITTEN per second, to be read beside blsw_fill_rate. order: 0 = consecutive workgroups take the same table chunk for different instances (what
+ * the engine launches), 1 = consecutive workgroups walk the chunks of one instance. Synchronous. */
+int blsw_keyset_broadcast_rate(const blsw_keyset_t* ks, uint64_t* d_witness, uint64_t witness_stride, uint64_t n, uint32_t order, uint32_t reps, double* bytes_per_s);
 /* average duration (ms) of the bit->Fp expansion kernel launches issued since the previous call (HIP events on the stream they
  * ran on, at most 1024 launches); blocks until they have finished and resets the statistics */
 int blsw_engine_expand_stats(blsw_engine_t* e, uint32_t* count, float* avg_ms);

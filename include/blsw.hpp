@@ -88,6 +88,55 @@ inline std::vector<uint8_t> unhex(std::string s, size_t want) {
 }
 }  // namespace detail
 
+// A key set shared by many aggregate_verify instances (blsw_keyset_t, ABI 15): the committee's K keys are allocated as witnesses ONCE, and every step of
+// an engine created with options.shared_keys = 1 that names the set gets the allocation witnesses copied into the head of its vectors. Owns the handle
+// and its device buffer; must outlive every step submitted with it. d_pks_xy: [K][12] u64 affine Montgomery on the device, (0, 0) = infinity (what
+// blsw_decode_batch writes). The submit / expand members are the engine's keyset entry points with this set as their `ks`.
+class KeySet {
+   public:
+    KeySet(const uint64_t* d_pks_xy, uint32_t n_keys, uint32_t output_form = 0, int device = -1, void* stream = nullptr) : n_keys_(n_keys) {
+        uint64_t bytes = 0;
+        check(blsw_keyset_bytes(n_keys, &bytes), "blsw_keyset_bytes");
+        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
+        buffer_ = detail::DeviceBytes(bytes);  // hipMalloc: 256-byte aligned
+        check(blsw_keyset_create(&ks_, d_pks_xy, n_keys, output_form, device, buffer_.get(), bytes, stream), "blsw_keyset_create");
+    }
+    KeySet(const KeySet&) = delete;
+    KeySet& operator=(const KeySet&) = delete;
+    KeySet(KeySet&& o) noexcept : ks_(o.ks_), n_keys_(o.n_keys_), buffer_(std::move(o.buffer_)) { o.ks_ = nullptr; }
+    ~KeySet() {
+        if (ks_) (void)blsw_keyset_destroy(ks_);
+    }
+    const blsw_keyset_t* get() const { return ks_; }
+    uint32_t n_keys() const { return n_keys_; }
+    // the table [n_keys * 1942][6] u64 on the device, in the set's output form
+    const uint64_t* table(uint64_t* n_elements = nullptr) const {
+        const uint64_t* t = nullptr;
+        uint64_t n = 0;
+        check(blsw_keyset_table(ks_, &t, &n), "blsw_keyset_table");
+        if (n_elements) *n_elements = n;
+        return t;
+    }
+    void submit_aggregate(blsw_engine_t* e, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg, uint64_t* d_instance, uint64_t* d_witness,
+                          uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream = nullptr) const {
+        check(blsw_engine_submit_aggregate_keyset(e, ks_, d_bitmap, d_sig_xy, d_msg, d_instance, d_witness, witness_stride, d_result, d_count, stream),
+              "blsw_engine_submit_aggregate_keyset");
+    }
+    void submit_aggregate_compact(blsw_engine_t* e, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg, void* d_compact, int32_t* d_result,
+                                  uint32_t* d_count, void* stream = nullptr) const {
+        check(blsw_engine_submit_aggregate_keyset_compact(e, ks_, d_bitmap, d_sig_xy, d_msg, d_compact, d_result, d_count, stream),
+              "blsw_engine_submit_aggregate_keyset_compact");
+    }
+    void expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t* d_witness, uint64_t witness_stride, void* stream = nullptr) const {
+        check(blsw_engine_expand_compact_keyset(e, ks_, d_compact, d_witness, witness_stride, stream), "blsw_engine_expand_compact_keyset");
+    }
+
+   private:
+    blsw_keyset_t* ks_ = nullptr;
+    uint32_t n_keys_ = 0;
+    detail::DeviceBytes buffer_;
+};
+
 // ark_r1cs_std::alloc::AllocationMode. PublicKeyVar / SignatureVar: Witness (the reference's circuits) or Input (the point's coordinates become
 // instance_assignment[1..]); ParametersVar: Constant or Witness.
 enum class AllocationMode { Constant, Input, Witness };
