@@ -154,6 +154,12 @@ def lib():
         L.blsw_engine_submit_aggregate_keyset.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
         L.blsw_engine_submit_aggregate_keyset_compact.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.blsw_engine_expand_compact_keyset.argtypes = [vp, vp, vp, vp, u64, vp]
+        L.blsw_compact_layout_keyset.argtypes = [u64, u32, ctypes.POINTER(blsw_engine_options_t), cl, ctypes.POINTER(u32)]
+        L.blsw_r1cs_head_rows.argtypes = [ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t), u64, ctypes.POINTER(u64)]
+        L.blsw_r1cs_handle_head_rows.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.blsw_r1cs_check_keyset.argtypes = [vp, vp, vp, vp, vp]
+        L.blsw_r1cs_check_compact_keyset.argtypes = [vp, cl, vp, vp, u32, vp, u64, vp, vp, vp]
+        L.blsw_r1cs_evaluate_compact_keyset.argtypes = [vp, cl, vp, vp, vp, u64, u64, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -169,7 +175,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_matrices_fill_aggregate_inputs", "blsw_engine_submit_aggregate_io", "blsw_compact_layout", "blsw_compact_locate",
                     "blsw_r1cs_check_compact", "blsw_r1cs_evaluate_compact", "blsw_keyset_bytes", "blsw_keyset_create", "blsw_keyset_table", "blsw_keyset_destroy",
                     "blsw_keyset_broadcast_rate", "blsw_engine_submit_aggregate_keyset", "blsw_engine_submit_aggregate_keyset_compact",
-                    "blsw_engine_expand_compact_keyset"]
+                    "blsw_engine_expand_compact_keyset", "blsw_compact_layout_keyset", "blsw_r1cs_head_rows", "blsw_r1cs_handle_head_rows", "blsw_r1cs_check_keyset",
+                    "blsw_r1cs_check_compact_keyset", "blsw_r1cs_evaluate_compact_keyset"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -278,6 +285,18 @@ def compact_layout(n, msg_len=32, **options):
     if rc:
         raise BlswError("blsw_compact_layout failed: %d" % rc)
     return c
+
+
+def compact_layout_keyset(n, msg_len=32, **options):
+    """blsw_compact_layout_keyset -> (layout, head_len) of the compact steps of a shared-keys engine (options with shared_keys=1): the layout of the
+    buffer, which carries no key rows, and the length of the head the receiver's KeySet supplies. Witness k of the caller's vector is table[k] for
+    k < head_len, else compact_locate(layout, k - head_len, lane). Host only."""
+    opt = options.pop("_opt", None) or engine_options(**options)
+    c, head = blsw_compact_layout_t(), ctypes.c_uint32(0)
+    rc = lib().blsw_compact_layout_keyset(n, msg_len, ctypes.byref(opt), ctypes.byref(c), ctypes.byref(head))
+    if rc:
+        raise BlswError("blsw_compact_layout_keyset failed: %d" % rc)
+    return c, head.value
 
 
 def compact_locate(layout, k, lane):
@@ -568,7 +587,10 @@ class WitnessEngine:
         return self._counter(lib().blsw_engine_compact_bytes)
 
     def compact_layout(self):
-        """blsw_compact_layout_t of this engine's compact steps (ConstraintChecker.which_is_unsatisfied_compact reads a step through it)"""
+        """blsw_compact_layout_t of this engine's compact steps (ConstraintChecker.which_is_unsatisfied_compact reads a step through it). A shared-keys
+        engine: the layout of the buffer alone (compact_layout_keyset; the head is the step's KeySet, passed to the checker as keyset=)."""
+        if self._opt.shared_keys:
+            return compact_layout_keyset(self.n, self.msg_len, _opt=self._opt)[0]
         return compact_layout(self.n, self.msg_len, _opt=self._opt)
 
     def new_compact_buffer(self, batches=1):
@@ -1111,6 +1133,17 @@ def r1cs_device_bytes(mats):
     return b.value
 
 
+def r1cs_head_rows(mats, head_len):
+    """blsw_r1cs_head_rows: the number of leading constraints of a matrices() dict that read nothing but column 0 and the first head_len witnesses
+    (host only; validates the CSR like r1cs_device_bytes)"""
+    info, m = _matrices_struct(mats)
+    rows = ctypes.c_uint64(0)
+    rc = lib().blsw_r1cs_head_rows(ctypes.byref(info), ctypes.byref(m), head_len, ctypes.byref(rows))
+    if rc:
+        raise BlswError("blsw_r1cs_head_rows failed: %d" % rc)
+    return rows.value
+
+
 class ConstraintChecker:
     """The constraint system of one circuit shape on the GPU (blsw_r1cs_*): arkworks' cs.is_satisfied() / cs.which_is_unsatisfied() and the
     A z, B z, C z rows, for a batch of witness vectors at once. Arguments as matrices(). Inputs are the tensors WitnessEngine writes:
@@ -1213,10 +1246,38 @@ class ConstraintChecker:
             raise BlswError("blsw_r1cs_evaluate failed: %d" % rc)
         return tuple(out)
 
-    def _io_compact(self, layout, compact, instance, stream):
+    def head_rows(self, n_keys):
+        """the number of leading constraints that read nothing but the constant one and the allocation witnesses of the first n_keys keys (elements
+        [0, n_keys * 1942) of the witness vector): the rows check_keyset evaluates and skip_head_rows=True leaves out (blsw_r1cs_handle_head_rows)."""
+        rows = ctypes.c_uint64(0)
+        rc = lib().blsw_r1cs_handle_head_rows(self._r, n_keys * SEG_PK_ALLOC, ctypes.byref(rows))
+        if rc:
+            raise BlswError("blsw_r1cs_handle_head_rows failed: %d" % rc)
+        return rows.value
+
+    def check_keyset(self, keyset, stream=None):
+        """the committee, once: (row, unreduced) of the head rows on z = [1 | keyset.table] — the first unsatisfied row or -1, and the index of z
+        (n_instance_vars + k) of the first table element >= p or -1. The table in either element form. Synchronises `stream`."""
+        torch = self.torch
+        assert isinstance(keyset, KeySet) and keyset.device == self.device
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if s != torch.cuda.current_stream(self.device):
+            self.buffer.record_stream(s)
+            keyset.buffer.record_stream(s)
+        with torch.cuda.stream(s):
+            out = torch.empty(2, dtype=torch.int64, device=self.device)
+        rc = lib().blsw_r1cs_check_keyset(self._r, keyset._ks, out[0:].data_ptr(), out[1:].data_ptr(), s.cuda_stream)
+        if rc:
+            raise BlswError("blsw_r1cs_check_keyset failed: %d" % rc)
+        with torch.cuda.stream(s):
+            row, unreduced = out.tolist()
+        return row, unreduced
+
+    def _io_compact(self, layout, compact, instance, stream, keyset=None):
         """-> (n, instance pointer, instance stride, stream) for a step's compact buffer (uint8 cuda tensor of layout.total bytes)"""
         torch = self.torch
         assert isinstance(layout, blsw_compact_layout_t)
+        assert keyset is None or (isinstance(keyset, KeySet) and keyset.device == self.device)
         assert compact.is_cuda and compact.device == self.device and compact.is_contiguous() and compact.dtype.itemsize == 1 and compact.numel() >= layout.total
         n, ip, ist = int(layout.n), None, 0
         if instance is not None:
@@ -1228,41 +1289,60 @@ class ConstraintChecker:
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         if s != torch.cuda.current_stream(self.device):
             self.buffer.record_stream(s)
+            if keyset is not None:
+                keyset.buffer.record_stream(s)
         return n, ip, ist, s
 
-    def _check_compact(self, layout, compact, instance, stream, want_unreduced):
-        n, ip, ist, s = self._io_compact(layout, compact, instance, stream)
+    def _check_compact(self, layout, compact, instance, stream, want_unreduced, keyset=None, skip_head_rows=False):
+        if keyset is None and skip_head_rows:
+            raise BlswError("skip_head_rows needs keyset=: only a shared-keys step has head rows to skip")
+        n, ip, ist, s = self._io_compact(layout, compact, instance, stream, keyset)
         with self.torch.cuda.stream(s):
             bad = self.torch.empty(n, dtype=self.torch.int64, device=self.device)
             unr = self.torch.empty(n, dtype=self.torch.int64, device=self.device) if want_unreduced else None
-        rc = lib().blsw_r1cs_check_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, bad.data_ptr(), unr.data_ptr() if unr is not None else None, s.cuda_stream)
+        up = unr.data_ptr() if unr is not None else None
+        if keyset is not None:
+            rc = lib().blsw_r1cs_check_compact_keyset(self._r, ctypes.byref(layout), compact.data_ptr(), keyset._ks, 1 if skip_head_rows else 0, ip, ist, bad.data_ptr(), up,
+                                                      s.cuda_stream)
+        else:
+            rc = lib().blsw_r1cs_check_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, bad.data_ptr(), up, s.cuda_stream)
         if rc:
-            raise BlswError("blsw_r1cs_check_compact failed: %d" % rc)
+            raise BlswError("blsw_r1cs_check_compact%s failed: %d" % ("_keyset" if keyset is not None else "", rc))
         return bad, unr
 
-    def which_is_unsatisfied_compact(self, layout, compact, instance=None, stream=None):
+    def which_is_unsatisfied_compact(self, layout, compact, instance=None, stream=None, keyset=None, skip_head_rows=False):
         """which_is_unsatisfied of the layout.n instances of a step read straight from its compact buffer (WitnessEngine.submit_compact /
-        compact_layout()): no expand_compact, no 34 MB-per-instance tensor. Montgomery form; instance as in which_is_unsatisfied."""
-        return self._check_compact(layout, compact, instance, stream, False)[0]
+        compact_layout()): no expand_compact, no 34 MB-per-instance tensor. Montgomery form; instance as in which_is_unsatisfied.
+        keyset: the step's KeySet (a shared-keys engine's step: its buffer carries no key rows, the set's table is the head of every vector).
+        skip_head_rows: leave out the rows that read the head alone (head_rows(keyset.n_keys) of them) — check_keyset vouches for those once per
+        set; reported rows keep their numbers."""
+        return self._check_compact(layout, compact, instance, stream, False, keyset, skip_head_rows)[0]
 
-    def is_satisfied_compact(self, layout, compact, instance=None, stream=None):
+    def is_satisfied_compact(self, layout, compact, instance=None, stream=None, keyset=None, skip_head_rows=False):
         """bool [layout.n]"""
-        return self.which_is_unsatisfied_compact(layout, compact, instance, stream) < 0
+        return self.which_is_unsatisfied_compact(layout, compact, instance, stream, keyset, skip_head_rows) < 0
 
-    def first_unreduced_compact(self, layout, compact, instance=None, stream=None):
-        """int64 [layout.n]: first index of z = [instance | witness] >= p among the instance vector and the staged rows (a bit cannot be), or -1"""
-        return self._check_compact(layout, compact, instance, stream, True)[1]
+    def first_unreduced_compact(self, layout, compact, instance=None, stream=None, keyset=None, skip_head_rows=False):
+        """int64 [layout.n]: first index of z = [instance | witness] >= p among the instance vector and the staged rows (a bit cannot be), or -1.
+        With keyset=: the buffer's witness k is reported at n_instance_vars + head_len + k; the head itself is never covered (check_keyset)."""
+        return self._check_compact(layout, compact, instance, stream, True, keyset, skip_head_rows)[1]
 
-    def evaluate_compact(self, layout, compact, instance=None, rows=None, stream=None):
-        """evaluate() with z read from a step's compact buffer: (az, bz, cz), int64 [layout.n, count, 6] each, Montgomery form"""
+    def evaluate_compact(self, layout, compact, instance=None, rows=None, stream=None, keyset=None, skip_head_rows=False):
+        """evaluate() with z read from a step's compact buffer: (az, bz, cz), int64 [layout.n, count, 6] each, Montgomery form. keyset: as in
+        which_is_unsatisfied_compact; any row window, head rows included (skip_head_rows has nothing to skip here and must stay False)."""
+        if skip_head_rows:
+            raise BlswError("evaluate_compact evaluates the window it is given: skip_head_rows does not apply")
         begin, count = rows if rows is not None else (0, self.n_constraints)
-        n, ip, ist, s = self._io_compact(layout, compact, instance, stream)
+        n, ip, ist, s = self._io_compact(layout, compact, instance, stream, keyset)
         with self.torch.cuda.stream(s):
             out = [self.torch.empty((n, count, 6), dtype=self.torch.int64, device=self.device) for _ in range(3)]
-        rc = lib().blsw_r1cs_evaluate_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, begin, count, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                              s.cuda_stream)
+        outs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), s.cuda_stream)
+        if keyset is not None:
+            rc = lib().blsw_r1cs_evaluate_compact_keyset(self._r, ctypes.byref(layout), compact.data_ptr(), keyset._ks, ip, ist, begin, count, *outs)
+        else:
+            rc = lib().blsw_r1cs_evaluate_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, begin, count, *outs)
         if rc:
-            raise BlswError("blsw_r1cs_evaluate_compact failed: %d" % rc)
+            raise BlswError("blsw_r1cs_evaluate_compact%s failed: %d" % ("_keyset" if keyset is not None else "", rc))
         return tuple(out)
 
 

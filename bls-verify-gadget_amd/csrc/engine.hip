@@ -106,12 +106,6 @@ struct GroupTrace {
     uint64_t lanes;
     bool lat;
 };
-struct blsw_keyset {
-    uint32_t n_keys = 0, form = 0;
-    int device = -1;
-    Fp* table = nullptr;  // [n_keys * SEG_PK_ALLOC] in `form`
-    Fp* proj = nullptr;   // [3][n_keys] Montgomery
-};
 struct blsw_engine {
     uint64_t n = 0;
     uint32_t msg_len = 0, max_steps = 0;
@@ -962,6 +956,17 @@ int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_
     blsw_layout_t L;
     options_layout(msg_len, options, &L);
     *out = compact_layout(n, L, Modes{options->pairing_mode == 0, options->g2_mode == 1});
+    return BLSW_OK;
+}
+// the compact steps of a shared-keys engine: the layout of the rows it computes (LR, the Keys-Input layout) and the length of the head the form does not
+// carry; host only
+int blsw_compact_layout_keyset(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, blsw_compact_layout_t* rows, uint32_t* head_len) {
+    if (!rows || !head_len || !options || n % 64 || options->n_pairs > 1 || !options->shared_keys) return BLSW_ERR_ARG;
+    if (int rc = check_options(n, msg_len, 2, 1, options)) return rc;
+    blsw_layout_t L;
+    options_layout_rows(msg_len, options, &L);
+    *rows = compact_layout(n, L, Modes{options->pairing_mode == 0, options->g2_mode == 1});
+    *head_len = options->n_keys * SEG_PK_ALLOC;
     return BLSW_OK;
 }
 int blsw_compact_locate(const blsw_compact_layout_t* layout, uint32_t k, uint64_t lane, uint32_t* region, uint64_t* byte_offset, uint32_t* bit) {

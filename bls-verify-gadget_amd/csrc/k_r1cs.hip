@@ -18,6 +18,10 @@
 // bit words and staged rows as they travel, blsw_compact_layout_t). The compact source evaluates compact_locate (kcommon.hpp) per entry: the column is
 // wave-uniform, so region and row are scalar arithmetic and the three-way branch does not diverge; a bit column is one u32 per lane, a tile row one
 // contiguous 3 KB read per wave — the instance-interleaved gather the expanded form cannot give.
+// A shared-keys step (ABI 15) carries no key rows: its z is [instance | the key set's table | the compact rows] (KeysetCompactArgs, ABI 16). A head column
+// is one address for all 64 lanes — wave-uniform like the column itself, so the fourth branch does not diverge either. The leading rows that read
+// nothing but the head (head_cover, r1cs_encode.hpp) are a function of the committee alone: blsw_r1cs_check_keyset evaluates them once per set
+// (the plain kernel, one instance whose witness vector is the table) and the step's check may then start at the first row behind them.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -58,6 +62,13 @@ struct CompactArgs : Args {
     const char* compact;
 };
 
+// z from a compact step of a shared-keys engine: witness k < head_len is element k of the step's key set, the same for every instance; the rest is
+// the compact buffer at k - head_len
+struct KeysetCompactArgs : CompactArgs {
+    const uint64_t* head;  // [head_len][6] Montgomery (blsw_keyset_table)
+    uint32_t head_len;
+};
+
 __device__ __forceinline__ Fp load_fp(const uint64_t* src) {
     const uint4* q = reinterpret_cast<const uint4*>(src);
     const uint4 a = q[0], b = q[1], c = q[2];
@@ -70,17 +81,28 @@ __device__ __forceinline__ Fp load_z(const Args& a, uint64_t i, uint32_t col) {
     return a.one;
 }
 
-__device__ __forceinline__ Fp load_z(const CompactArgs& a, uint64_t i, uint32_t col) {
-    if (col >= a.n_inst) {
-        uint64_t off;
-        uint32_t bit;
-        const uint64_t lane = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(i >> 6)) << 6) | (i & 63);  // the tile is wave-uniform: scalar address terms
-        if (compact_locate(a.c, col - a.n_inst, lane, &off, &bit) != BLSW_COMPACT_BIT) return load_fp(reinterpret_cast<const uint64_t*>(a.compact + off));
-        const uint32_t m = 0u - ((*reinterpret_cast<const uint32_t*>(a.compact + off) >> bit) & 1u);
-        Fp r;
+// witness k of instance i of a compact buffer
+__device__ __forceinline__ Fp load_compact(const CompactArgs& a, uint64_t i, uint32_t k) {
+    uint64_t off;
+    uint32_t bit;
+    const uint64_t lane = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(i >> 6)) << 6) | (i & 63);  // the tile is wave-uniform: scalar address terms
+    if (compact_locate(a.c, k, lane, &off, &bit) != BLSW_COMPACT_BIT) return load_fp(reinterpret_cast<const uint64_t*>(a.compact + off));
+    const uint32_t m = 0u - ((*reinterpret_cast<const uint32_t*>(a.compact + off) >> bit) & 1u);
+    Fp r;
 #pragma unroll
-        for (int j = 0; j < 12; j++) r.l[j] = a.one.l[j] & m;
-        return r;
+    for (int j = 0; j < 12; j++) r.l[j] = a.one.l[j] & m;
+    return r;
+}
+__device__ __forceinline__ Fp load_z(const CompactArgs& a, uint64_t i, uint32_t col) {
+    if (col >= a.n_inst) return load_compact(a, i, col - a.n_inst);
+    if (a.inst) return load_fp(a.inst + (i * a.inst_stride + col) * 6);
+    return a.one;
+}
+__device__ __forceinline__ Fp load_z(const KeysetCompactArgs& a, uint64_t i, uint32_t col) {
+    if (col >= a.n_inst) {
+        const uint32_t k = col - a.n_inst;
+        if (k < a.head_len) return load_fp(a.head + (uint64_t)k * 6);  // one address for the wave
+        return load_compact(a, i, k - a.head_len);
     }
     if (a.inst) return load_fp(a.inst + (i * a.inst_stride + col) * 6);
     return a.one;
@@ -159,8 +181,8 @@ __global__ __launch_bounds__(256) void k_r1cs_unreduced(const uint64_t* __restri
 
 // the same over the staged rows of a compact step (a bit cannot be unreduced): grid (chunks, 64-instance tiles), lane = instance, a wave takes one
 // staged row at a time — 3 KB contiguous below split_row. j counts the witnesses outside the SHA segment; the moved segment makes a thread's
-// indices non-monotonic, so every hit goes to the atomic.
-__global__ __launch_bounds__(256) void k_r1cs_unreduced_compact(blsw_compact_layout_t c, const char* __restrict__ compact, uint32_t n_inst, unsigned long long* __restrict__ out) {
+// indices non-monotonic, so every hit goes to the atomic. base = the index of z of the buffer's witness 0 (n_inst, plus the head of a shared-keys step).
+__global__ __launch_bounds__(256) void k_r1cs_unreduced_compact(blsw_compact_layout_t c, const char* __restrict__ compact, uint32_t base, unsigned long long* __restrict__ out) {
     constexpr uint32_t P[12] = BLSW_P_LIMBS;
     const uint64_t i = (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);
 #pragma unroll 1
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(256) void k_r1cs_unreduced_compact(blsw_compact_lay
         uint32_t borrow = 0;
 #pragma unroll
         for (int l = 0; l < 12; l++) subb32(z.l[l], P[l], borrow);
-        if (!borrow) atomicMin(out + i, (unsigned long long)n_inst + k);
+        if (!borrow) atomicMin(out + i, (unsigned long long)base + k);
     }
 }
 
@@ -192,7 +214,8 @@ struct blsw_r1cs {
     int device;
     uint64_t n_cons, n_inst, n_wit;
     Enc enc;
-    std::vector<uint64_t> blk;  // host copy of the block starts (evaluate's row range -> blocks)
+    std::vector<uint64_t> blk;  // host copy of the block starts (a row range -> blocks)
+    std::vector<uint32_t> head;  // head_cover (r1cs_encode.hpp): the head rows of any head_len without the CSR
 };
 
 int blsw_r1cs_device_bytes(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t* bytes) {
@@ -201,6 +224,16 @@ int blsw_r1cs_device_bytes(const blsw_matrices_info_t* info, const blsw_matrices
     const int rc = encode(info, m, &e);
     if (rc) return rc;
     *bytes = e.bytes;
+    return BLSW_OK;
+}
+
+int blsw_r1cs_head_rows(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t head_len, uint64_t* rows) {
+    if (!rows) return BLSW_ERR_ARG;
+    Encoded e;
+    const int rc = encode(info, m, &e);
+    if (rc) return rc;
+    if (head_len > info->n_witness) return BLSW_ERR_ARG;
+    *rows = head_rows(head_cover(info, m), head_len);
     return BLSW_OK;
 }
 
@@ -240,6 +273,7 @@ int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const 
     r->enc.table = reinterpret_cast<const Fp*>(base + e.off_table);
     r->enc.blk = reinterpret_cast<const uint64_t*>(base + e.off_blk);
     r->blk = std::move(e.blk);
+    r->head = head_cover(info, m);
     *out = r;
     return BLSW_OK;
 }
@@ -312,6 +346,15 @@ int launch(const CompactArgs& a, bool eval, hipStream_t st) {
     return hip_ok(hipGetLastError(), "launch");
 }
 
+int launch(const KeysetCompactArgs& a, bool eval, hipStream_t st) {
+    dim3 grid((a.n_blk + WAVES - 1) / WAVES, (unsigned)(a.n / 64));
+    if (eval)
+        hipLaunchKernelGGL((k_r1cs<true, KeysetCompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_r1cs<false, KeysetCompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
+    return hip_ok(hipGetLastError(), "launch");
+}
+
 struct Guard {
     int prev = -1;
     bool switched = false;
@@ -327,17 +370,26 @@ struct Guard {
 
 namespace {
 
-// the whole matrix, first unsatisfied row per instance
+// rows [row_lo, row_hi) and the blocks that hold them (the first and the last block are clamped to the range by the kernel)
 template <class A>
-int run_check(const blsw_r1cs* r, A& a, uint32_t form, int64_t* d_first_unsatisfied, hipStream_t st) {
+void set_rows(const blsw_r1cs* r, A& a, uint64_t row_lo, uint64_t row_hi) {
+    a.row_lo = row_lo;
+    a.row_hi = row_hi;
+    const auto& blk = r->blk;
+    const uint64_t b0 = (uint64_t)(std::upper_bound(blk.begin(), blk.end(), row_lo) - blk.begin()) - 1;
+    const uint64_t b1 = (uint64_t)(std::lower_bound(blk.begin(), blk.end(), row_hi) - blk.begin());
+    a.blk_first = (uint32_t)b0;
+    a.n_blk = (uint32_t)(b1 - b0);
+}
+// rows [row_lo, row_hi) (reported as they are numbered in the matrix), first unsatisfied row per instance
+template <class A>
+int run_check(const blsw_r1cs* r, A& a, uint32_t form, uint64_t row_lo, uint64_t row_hi, int64_t* d_first_unsatisfied, hipStream_t st) {
     static constexpr uint32_t R2[12] = BLSW_R2_LIMBS, R3[12] = BLSW_R3_LIMBS;
     a.k = fp_const(form ? R3 : R2);
-    a.blk_first = 0;
-    a.n_blk = (uint32_t)(r->blk.size() - 1);
-    a.row_lo = 0;
-    a.row_hi = r->n_cons;
     a.bad = reinterpret_cast<uint64_t*>(d_first_unsatisfied);
     if (hip_ok(hipMemsetAsync(d_first_unsatisfied, 0xFF, a.n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;  // all ones = -1 = satisfied
+    if (row_lo >= row_hi) return BLSW_OK;  // no row to check (a set without head rows)
+    set_rows(r, a, row_lo, row_hi);
     return launch(a, false, st);
 }
 // rows [row_begin, row_begin + row_count) of A z, B z, C z
@@ -345,14 +397,7 @@ template <class A>
 int run_evaluate(const blsw_r1cs* r, A& a, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, hipStream_t st) {
     static constexpr uint32_t R2[12] = BLSW_R2_LIMBS;
     a.k = fp_const(R2);
-    a.row_lo = row_begin;
-    a.row_hi = row_begin + row_count;
-    // blocks [b0, b1) that hold rows of the range
-    const auto& blk = r->blk;
-    const uint64_t b0 = (uint64_t)(std::upper_bound(blk.begin(), blk.end(), a.row_lo) - blk.begin()) - 1;
-    const uint64_t b1 = (uint64_t)(std::lower_bound(blk.begin(), blk.end(), a.row_hi) - blk.begin());
-    a.blk_first = (uint32_t)b0;
-    a.n_blk = (uint32_t)(b1 - b0);
+    set_rows(r, a, row_begin, row_begin + row_count);
     a.out[0] = d_az;
     a.out[1] = d_bz;
     a.out[2] = d_cz;
@@ -362,8 +407,8 @@ bool row_window_ok(const blsw_r1cs* r, uint64_t row_begin, uint64_t row_count) {
     return row_count != 0 && row_begin < r->n_cons && row_count <= r->n_cons - row_begin;
 }
 // the argument rules of the compact calls (host only), and their arguments
-int compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride) {
-    if (!r || !c || !d_compact || (reinterpret_cast<uintptr_t>(d_compact) & 15) || !compact_layout_ok(*c) || c->n_witness != r->n_wit) return BLSW_ERR_ARG;
+int compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride, uint64_t head_len = 0) {
+    if (!r || !c || !d_compact || (reinterpret_cast<uintptr_t>(d_compact) & 15) || !compact_layout_ok(*c) || c->n_witness + head_len != r->n_wit) return BLSW_ERR_ARG;
     if (r->n_inst > 1 && (!d_instance || instance_stride < r->n_inst)) return BLSW_ERR_ARG;
     if (d_instance && instance_stride < r->n_inst) return BLSW_ERR_ARG;
     return BLSW_OK;
@@ -375,6 +420,40 @@ CompactArgs make_compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c
     a.compact = reinterpret_cast<const char*>(d_compact);
     return a;
 }
+// the rules of the calls that take a key set (host only): a set on the handle's device whose table is no longer than the witness vector
+bool keyset_ok(const blsw_r1cs* r, const blsw_keyset* ks) { return r && ks && ks->device == r->device && (uint64_t)ks->n_keys * SEG_PK_ALLOC <= r->n_wit; }
+// ... of the two compact calls: the set's table is the head of z beside the buffer's Montgomery elements
+int keyset_compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const blsw_keyset* ks, uint32_t head_rows_mode, const uint64_t* d_instance,
+                        uint64_t instance_stride) {
+    if (!keyset_ok(r, ks) || ks->form != 0 || head_rows_mode > BLSW_R1CS_HEAD_SKIP) return BLSW_ERR_ARG;
+    return compact_args(r, c, d_compact, d_instance, instance_stride, (uint64_t)ks->n_keys * SEG_PK_ALLOC);
+}
+KeysetCompactArgs make_keyset_compact_args(const blsw_r1cs* r, const blsw_compact_layout_t* c, const void* d_compact, const blsw_keyset* ks, const uint64_t* d_instance,
+                                           uint64_t instance_stride) {
+    KeysetCompactArgs a;
+    static_cast<CompactArgs&>(a) = make_compact_args(r, c, d_compact, d_instance, instance_stride);
+    a.head = reinterpret_cast<const uint64_t*>(ks->table);
+    a.head_len = ks->n_keys * SEG_PK_ALLOC;
+    return a;
+}
+// the unreduced elements of a compact step: the instance vectors (plain: the pass over the first n_inst indices of z; atomicMin: any order with the
+// rows) and the staged rows, reported from index `base` of z on
+int unreduced_compact(const blsw_r1cs* r, const blsw_compact_layout_t* layout, const char* compact, const uint64_t* d_instance, uint64_t instance_stride, uint32_t base,
+                      int64_t* d_first_unreduced, hipStream_t st) {
+    const uint64_t n = layout->n;
+    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
+    unsigned long long* unr = reinterpret_cast<unsigned long long*>(d_first_unreduced);
+    if (d_instance) {
+        for (uint64_t first = 0; first < n; first += 65535) {
+            const uint64_t cnt = n - first < 65535 ? n - first : 65535;
+            hipLaunchKernelGGL(k_r1cs_unreduced, dim3(1, (unsigned)cnt), dim3(256), 0, st, d_instance + first * instance_stride * 6, instance_stride, nullptr, 0,
+                               (uint32_t)r->n_inst, r->n_inst, unr + first);
+        }
+    }
+    const uint32_t chunks = (layout->staging_rows + 3) / 4;
+    if (chunks) hipLaunchKernelGGL(k_r1cs_unreduced_compact, dim3(chunks < 256 ? chunks : 256, (unsigned)(n / 64)), dim3(256), 0, st, *layout, compact, base, unr);
+    return hip_ok(hipGetLastError(), "launch");
+}
 
 }  // namespace
 
@@ -384,7 +463,7 @@ int blsw_r1cs_check(blsw_r1cs_t* r, const uint64_t* d_instance, uint64_t instanc
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     Guard guard(r->device);
     Args a = make_args(r, d_instance, instance_stride, d_witness, witness_stride, n, form);
-    int rc = run_check(r, a, form, d_first_unsatisfied, st);
+    int rc = run_check(r, a, form, 0, r->n_cons, d_first_unsatisfied, st);
     if (rc || !d_first_unreduced) return rc;
     if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
     const uint64_t n_z = r->n_inst + r->n_wit, chunks = (n_z + 255) / 256;
@@ -414,21 +493,9 @@ int blsw_r1cs_check_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     Guard guard(r->device);
     CompactArgs a = make_compact_args(r, layout, d_compact, d_instance, instance_stride);
-    int rc = run_check(r, a, 0, d_first_unsatisfied, st);
+    int rc = run_check(r, a, 0, 0, r->n_cons, d_first_unsatisfied, st);
     if (rc || !d_first_unreduced) return rc;
-    const uint64_t n = layout->n;
-    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
-    unsigned long long* unr = reinterpret_cast<unsigned long long*>(d_first_unreduced);
-    if (d_instance) {  // the instance vectors are plain: the existing pass over the first n_inst indices of z (atomicMin: any order with the rows)
-        for (uint64_t first = 0; first < n; first += 65535) {
-            const uint64_t cnt = n - first < 65535 ? n - first : 65535;
-            hipLaunchKernelGGL(k_r1cs_unreduced, dim3(1, (unsigned)cnt), dim3(256), 0, st, d_instance + first * instance_stride * 6, instance_stride, nullptr, 0,
-                               (uint32_t)r->n_inst, r->n_inst, unr + first);
-        }
-    }
-    const uint32_t chunks = (layout->staging_rows + 3) / 4;
-    if (chunks) hipLaunchKernelGGL(k_r1cs_unreduced_compact, dim3(chunks < 256 ? chunks : 256, (unsigned)(n / 64)), dim3(256), 0, st, *layout, a.compact, (uint32_t)r->n_inst, unr);
-    return hip_ok(hipGetLastError(), "launch");
+    return unreduced_compact(r, layout, a.compact, d_instance, instance_stride, (uint32_t)r->n_inst, d_first_unreduced, st);
 }
 
 int blsw_r1cs_evaluate_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
@@ -437,5 +504,51 @@ int blsw_r1cs_evaluate_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layo
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     Guard guard(r->device);
     CompactArgs a = make_compact_args(r, layout, d_compact, d_instance, instance_stride);
+    return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
+}
+
+int blsw_r1cs_handle_head_rows(const blsw_r1cs_t* r, uint64_t head_len, uint64_t* rows) {
+    if (!r || !rows || head_len > r->n_wit) return BLSW_ERR_ARG;
+    *rows = head_rows(r->head, head_len);
+    return BLSW_OK;
+}
+
+// ABI 16: the committee once, and a shared-keys step from its compact buffer plus the receiver's key set
+int blsw_r1cs_check_keyset(blsw_r1cs_t* r, const blsw_keyset_t* ks, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (!keyset_ok(r, ks) || !d_first_unsatisfied) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    // one instance whose witness vector is the table: the head rows read nothing else (and column 0, the constant one in the table's form)
+    const uint64_t head_len = (uint64_t)ks->n_keys * SEG_PK_ALLOC;
+    const uint64_t* table = reinterpret_cast<const uint64_t*>(ks->table);
+    Args a = make_args(r, nullptr, 0, table, head_len, 1, ks->form);
+    int rc = run_check(r, a, ks->form, 0, head_rows(r->head, head_len), d_first_unsatisfied, st);
+    if (rc || !d_first_unreduced) return rc;
+    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
+    const uint64_t n_z = r->n_inst + head_len, chunks = (n_z + 255) / 256;
+    hipLaunchKernelGGL(k_r1cs_unreduced, dim3((unsigned)(chunks < 64 ? chunks : 64), 1), dim3(256), 0, st, nullptr, 0, table, head_len, (uint32_t)r->n_inst, n_z,
+                       reinterpret_cast<unsigned long long*>(d_first_unreduced));
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+int blsw_r1cs_check_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* rows_layout, const void* d_compact, const blsw_keyset_t* ks, uint32_t head_rows_mode,
+                                   const uint64_t* d_instance, uint64_t instance_stride, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (keyset_compact_args(r, rows_layout, d_compact, ks, head_rows_mode, d_instance, instance_stride) || !d_first_unsatisfied) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    KeysetCompactArgs a = make_keyset_compact_args(r, rows_layout, d_compact, ks, d_instance, instance_stride);
+    const uint64_t row_lo = head_rows_mode == BLSW_R1CS_HEAD_SKIP ? head_rows(r->head, a.head_len) : 0;
+    int rc = run_check(r, a, 0, row_lo, r->n_cons, d_first_unsatisfied, st);
+    if (rc || !d_first_unreduced) return rc;
+    return unreduced_compact(r, rows_layout, a.compact, d_instance, instance_stride, (uint32_t)r->n_inst + a.head_len, d_first_unreduced, st);
+}
+
+int blsw_r1cs_evaluate_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* rows_layout, const void* d_compact, const blsw_keyset_t* ks, const uint64_t* d_instance,
+                                      uint64_t instance_stride, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream) {
+    if (keyset_compact_args(r, rows_layout, d_compact, ks, 0, d_instance, instance_stride) || !d_az || !d_bz || !d_cz || !row_window_ok(r, row_begin, row_count))
+        return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    KeysetCompactArgs a = make_keyset_compact_args(r, rows_layout, d_compact, ks, d_instance, instance_stride);
     return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
 }

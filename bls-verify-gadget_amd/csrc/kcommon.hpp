@@ -694,3 +694,11 @@ void launch_verify_values(uint64_t n, const Workspace& ws, const uint64_t* pk_xy
                           hipStream_t st);
 
 }  // namespace blsw
+
+// blsw_keyset_t (include/blsw.h, ABI 15): engine.hip creates it; the compact checker of a shared-keys step (k_r1cs.hip) reads its table as the head of z
+struct blsw_keyset {
+    uint32_t n_keys = 0, form = 0;
+    int device = -1;
+    blsw::Fp* table = nullptr;  // [n_keys * SEG_PK_ALLOC] in `form`
+    blsw::Fp* proj = nullptr;   // [3][n_keys] Montgomery
+};

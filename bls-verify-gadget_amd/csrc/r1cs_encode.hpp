@@ -128,5 +128,38 @@ inline int encode(const blsw_matrices_info_t* info, const blsw_matrices_t* m, En
     return BLSW_OK;
 }
 
+// Head rows (blsw_r1cs_head_rows, blsw_r1cs_check_keyset): cover[r] = the smallest head_len for which rows 0..r read nothing but column 0 and
+// witnesses below head_len, i.e. columns in [n_instance_vars, n_instance_vars + head_len). Non-decreasing; cut at the first row that reads a public
+// input (no head covers it). Of a CSR encode() has accepted.
+inline std::vector<uint32_t> head_cover(const blsw_matrices_info_t* info, const blsw_matrices_t* m) {
+    std::vector<uint32_t> cover;
+    cover.reserve(info->n_constraints);
+    const uint32_t n_inst = (uint32_t)info->n_instance_vars;
+    uint32_t need = 0;
+    for (uint64_t r = 0; r < info->n_constraints; r++) {
+        for (int mi = 0; mi < 3; mi++)
+            for (uint64_t k = m->row_ptr[mi][r]; k < m->row_ptr[mi][r + 1]; k++) {
+                const uint32_t c = m->col[mi][k];
+                if (c == 0) continue;
+                if (c < n_inst) return cover;
+                if (c - n_inst + 1 > need) need = c - n_inst + 1;
+            }
+        cover.push_back(need);
+    }
+    return cover;
+}
+// the number of leading rows a head of head_len witnesses covers
+inline uint64_t head_rows(const std::vector<uint32_t>& cover, uint64_t head_len) {
+    uint64_t lo = 0, hi = cover.size();
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (cover[mid] <= head_len)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace r1cs
 }  // namespace blsw

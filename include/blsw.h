@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 15
+#define BLSW_ABI_VERSION 16
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -379,7 +379,8 @@ int blsw_keyset_destroy(blsw_keyset_t* ks);
  * rows (blsw_engine_compact_bytes is smaller by n * K * 1942 * 48 bytes): the receiver supplies the set when it expands. BLSW_ERR_ARG: an engine
  * without shared_keys, a NULL set, a set whose n_keys, output_form or device differ from the engine's. The entry points that take d_pks_xy
  * (blsw_engine_submit_aggregate, _io, _compact) and blsw_engine_expand_compact refuse an engine with shared_keys; blsw_compact_layout refuses the
- * option (the compact checker has no head region yet). */
+ * option: its struct describes the buffer, and a shared-keys step's buffer is not the whole witness vector. blsw_compact_layout_keyset (ABI 16,
+ * below) gives the buffer's layout and the length of the head, and blsw_r1cs_check_compact_keyset checks such a step from the two. */
 int blsw_engine_submit_aggregate_keyset(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
                                         uint64_t* d_instance, uint64_t* d_witness, uint64_t witness_stride, int32_t* d_result, uint32_t* d_count, void* stream);
 int blsw_engine_submit_aggregate_keyset_compact(blsw_engine_t* e, const blsw_keyset_t* ks, const uint8_t* d_bitmap, const uint64_t* d_sig_xy, const uint8_t* d_msg,
@@ -480,6 +481,41 @@ int blsw_r1cs_check_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout,
                             int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
 int blsw_r1cs_evaluate_compact(blsw_r1cs_t* r, const blsw_compact_layout_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
                                uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
+/* ABI 16: a shared-keys step (options.shared_keys, ABI 15) checked from its compact buffer plus the receiver's key set, and the committee checked once
+ * per set instead of once per instance.
+ * The buffer of such a step is the compact form of the rows the engine computes — the circuit without its keys segment, field for field the layout
+ * of agg_inputs | BLSW_AGG_KEYS_INPUT — so blsw_compact_layout_t describes it unchanged; the head is the set's table and travels nowhere.
+ *   blsw_compact_layout_keyset: options->shared_keys must be 1, otherwise the rules of blsw_compact_layout. *rows = the layout of the buffer
+ *     (rows->total == blsw_engine_compact_bytes of such an engine; rows->n_witness = the caller-visible witness count - *head_len);
+ *     *head_len = n_keys * 1942. Witness k of the caller's vector is table[k] for k < *head_len, else blsw_compact_locate(rows, k - *head_len, lane).
+ *     Host only.
+ *   blsw_r1cs_head_rows: the number of leading constraints whose every column is 0 or in [n_instance_vars, n_instance_vars + head_len) — the rows
+ *     that are a function of the head alone (1 939 per key of the aggregate circuit: 1 939 * K for head_len = K * 1942). head_len 0 gives 0.
+ *     BLSW_ERR_ARG: a NULL pointer, a CSR blsw_r1cs_create refuses, head_len > n_witness. Host only. blsw_r1cs_handle_head_rows answers the same
+ *     for the matrices a handle was created from (create keeps the smallest covering head_len of every leading row on the host, not the CSR).
+ *   blsw_r1cs_check_keyset: the committee, once — rows [0, P) on z = [1 | table], P = the head rows of the set's n_keys * 1942 elements. The table
+ *     may be in either element form (blsw_keyset_create's output_form). d_first_unsatisfied [1] as blsw_r1cs_check; d_first_unreduced [1] (may be
+ *     NULL): the first table element >= p, reported as n_instance_vars + k. BLSW_ERR_ARG: a NULL handle, set or output, a set on another device
+ *     than the handle, a table longer than the handle's witness count.
+ *   blsw_r1cs_check_compact_keyset / _evaluate_compact_keyset: blsw_r1cs_check_compact / _evaluate_compact with z = [instance | table | buffer].
+ *     head_rows_mode BLSW_R1CS_HEAD_CHECK: every row for every instance; the verdict is that of blsw_r1cs_check on the step's expansion
+ *     (blsw_engine_expand_compact_keyset). BLSW_R1CS_HEAD_SKIP: rows [P, n_constraints) only, reported as they are numbered in the matrix — the
+ *     caller vouches for the set with blsw_r1cs_check_keyset (once per set, not per step). d_first_unreduced covers the instance vector and the
+ *     staged rows of the buffer, reported at n_instance_vars + head_len + k for the buffer's witness k; it NEVER covers the head, in either
+ *     mode: that is blsw_r1cs_check_keyset's. The evaluation takes any row window, head rows included.
+ *     BLSW_ERR_ARG before any HIP call, nothing written: every rule of the ABI 14 calls, a NULL set, a set on another device than the handle,
+ *     rows_layout->n_witness + n_keys * 1942 != the handle's witness count, head_rows_mode > 1, a set whose table is not Montgomery form
+ *     (output_form 1: the buffer's elements never are canonical). */
+#define BLSW_R1CS_HEAD_CHECK 0
+#define BLSW_R1CS_HEAD_SKIP 1
+int blsw_compact_layout_keyset(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, blsw_compact_layout_t* rows, uint32_t* head_len);
+int blsw_r1cs_head_rows(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t head_len, uint64_t* rows);
+int blsw_r1cs_handle_head_rows(const blsw_r1cs_t* r, uint64_t head_len, uint64_t* rows);
+int blsw_r1cs_check_keyset(blsw_r1cs_t* r, const blsw_keyset_t* ks, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+int blsw_r1cs_check_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* rows_layout, const void* d_compact, const blsw_keyset_t* ks, uint32_t head_rows_mode,
+                                   const uint64_t* d_instance, uint64_t instance_stride, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+int blsw_r1cs_evaluate_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* rows_layout, const void* d_compact, const blsw_keyset_t* ks, const uint64_t* d_instance,
+                                      uint64_t instance_stride, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
 
 /* Input decode (PublicKey::try_from / Signature::try_from -> deserialize_compressed, src/bls.rs:219-242, 316-339):
  *   d_pk48 [n][48], d_sig96 [n][96]  ZCash-format compressed points

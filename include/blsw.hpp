@@ -219,6 +219,36 @@ class ConstraintSystem {
         d_bad.download(bad.data(), layout.n * 8);
         return bad;
     }
+    // The same for a step of a shared-keys engine (blsw_r1cs_check_compact_keyset): its buffer carries no key rows, `layout` is blsw_compact_layout_keyset's
+    // and the head of every vector is the receiver's own KeySet (Montgomery form). skip_head_rows: only the rows behind the ones that read the head
+    // alone — check(keys) vouches for those, once per set instead of once per instance. Reported rows keep their numbers either way.
+    std::vector<int64_t> which_is_unsatisfied(const blsw_compact_layout_t& layout, const void* d_compact, const KeySet& keys, bool skip_head_rows,
+                                              const uint64_t* d_instance = nullptr) {
+        if (!r1cs_) build_checker();
+        if (layout_.n_instance_vars > 1 && !d_instance) {
+            if (!instance_.get() || layout.n != n_) throw Error("which_is_unsatisfied(compact, keys): instance vectors of layout.n systems", BLSW_ERR_ARG);
+            d_instance = static_cast<const uint64_t*>(instance_.get());
+        }
+        detail::DeviceBytes d_bad(layout.n * 8);
+        check(blsw_r1cs_check_compact_keyset(r1cs_, &layout, d_compact, keys.get(), skip_head_rows ? BLSW_R1CS_HEAD_SKIP : BLSW_R1CS_HEAD_CHECK, d_instance,
+                                             d_instance ? layout_.n_instance_vars : 0, static_cast<int64_t*>(d_bad.get()), nullptr, nullptr),
+              "blsw_r1cs_check_compact_keyset");
+        std::vector<int64_t> bad(layout.n);
+        d_bad.download(bad.data(), layout.n * 8);
+        return bad;
+    }
+    // The committee, once (blsw_r1cs_check_keyset): the first unsatisfied one of the rows that read nothing but the set's table, or -1; *first_unreduced
+    // (optional): the index of z of the first table element >= p, or -1. The table in either element form.
+    int64_t check(const KeySet& keys, int64_t* first_unreduced = nullptr) {
+        if (!r1cs_) build_checker();
+        detail::DeviceBytes d_out(16);
+        int64_t* d = static_cast<int64_t*>(d_out.get());
+        check(blsw_r1cs_check_keyset(r1cs_, keys.get(), d, first_unreduced ? d + 1 : nullptr, nullptr), "blsw_r1cs_check_keyset");
+        int64_t out[2] = {-1, -1};
+        d_out.download(out, first_unreduced ? 16 : 8);
+        if (first_unreduced) *first_unreduced = out[1];
+        return out[0];
+    }
     // cs.is_satisfied() of system i (one check of all n systems per call: call which_is_unsatisfied() once for a whole batch)
     bool is_satisfied(size_t i) {
         if (i >= n_) throw Error("is_satisfied out of range", BLSW_ERR_ARG);
@@ -251,6 +281,8 @@ class ConstraintSystem {
     std::array<int32_t, 2> status(size_t i) const { return {status_.at(2 * i), status_.at(2 * i + 1)}; }
 
    private:
+    // check(const KeySet&) hides the namespace's check(rc, what) inside this class: the same function, as an overload of the member
+    static void check(int rc, const char* what) { blsw::check(rc, what); }
     friend class ParametersVar;
     friend class UInt8;
     friend class PublicKeyVar;

@@ -14,7 +14,17 @@ call; median / min / max of --reps >= 5 calls each):
     check_compact       blsw_r1cs_check_compact on the buffer itself
 and the same pair for A z, B z, C z over a window of --eval-rows rows at the pairing tail (expand + evaluate / evaluate_compact).
 
-    python tools/r1cs_rate.py --compact [--n 1024] [--reps 5] [--steps 2] [--eval-rows 20000]"""
+    python tools/r1cs_rate.py --compact [--n 1024] [--reps 5] [--steps 2] [--eval-rows 20000]
+
+--keyset: from a SHARED-KEYS step (options.shared_keys) in compact wire form to a verdict at committee size, four legs interleaved in one process over
+the same steps (HIP-event time per call; median / min / max of --reps >= 5 calls each):
+    expand_then_check     (a) blsw_engine_expand_compact_keyset into n witness vectors, then blsw_r1cs_check on them (the only route before ABI 16)
+    check_compact         (b) blsw_r1cs_check_compact_keyset, BLSW_R1CS_HEAD_CHECK: every row for every instance, from the buffer and the set's table
+    check_compact_skip    (c) the same with BLSW_R1CS_HEAD_SKIP: the rows behind the head rows only
+    check_keyset          (d) blsw_r1cs_check_keyset alone: the committee's head rows, once per set
+The yardstick of every leg is (a). Every GPU step runs under a time limit; when one expires or fails the process ends there and nothing follows.
+
+    python tools/r1cs_rate.py --keyset [--n 128] [--keys 512] [--reps 5] [--steps 2] [--limit 240]"""
 import argparse
 import importlib
 import json
@@ -125,17 +135,100 @@ def compact_legs(a):
     print(json.dumps(out))
 
 
+def keyset_legs(a):
+    """--keyset: the routes from a shared-keys compact step to a verdict, alternating, over the same steps"""
+    import torch
+
+    from tools.agg_inputs_rate import StepLimit
+
+    pkg = importlib.import_module("bls-verify-gadget_amd")
+    workload = importlib.import_module("bls-verify-gadget_amd.workload")
+    dev = torch.device("cuda:0")
+    reps = max(5, a.reps)
+    n = a.n
+    K = a.keys
+    t0 = time.time()
+    mats = pkg.matrices(32, n_keys=K)
+    t_mats = time.time() - t0
+    with StepLimit(a.limit, "set-up"):
+        chk = pkg.ConstraintChecker.from_matrices(mats, dev)
+        pk, msg, sig, _ = workload.make_batch(pkg, max(n * a.steps, K), device=dev, tamper_every=0)
+        keyset = pkg.KeySet(pk[:K].contiguous())
+        bitmap = (torch.arange(n * K, device=dev).reshape(n, K) % 3 != 0).to(torch.uint8).contiguous()  # two thirds of the committee signed
+        eng = pkg.WitnessEngine(n, 32, max_steps=2, n_buffers=2, device=dev, n_keys=K, shared_keys=1)
+        lay = eng.compact_layout()
+        assert lay.total == eng.compact_bytes() and lay.n_witness + K * pkg.SEG_PK_ALLOC == chk.n_witness
+        comp = eng.new_compact_buffer(a.steps)
+        for s in range(a.steps):  # the signatures do not match the bitmaps: the gadget's Boolean is false, the assignment still satisfies the system
+            eng.submit_aggregate_keyset_compact(keyset, bitmap, sig[s * n:(s + 1) * n].contiguous(), msg[s * n:(s + 1) * n].contiguous(), comp[s])
+        eng.flush()
+        torch.cuda.synchronize()
+        w = eng.new_witness_tensor()  # the receiver's n expanded vectors (leg a only)
+    head_rows = chk.head_rows(K)
+
+    def leg_a(s):
+        eng.expand_compact(comp[s], w, keyset=keyset)
+        return chk.which_is_unsatisfied(w)
+
+    legs = {"expand_then_check": leg_a,
+            "check_compact": lambda s: chk.which_is_unsatisfied_compact(lay, comp[s], keyset=keyset),
+            "check_compact_skip": lambda s: chk.which_is_unsatisfied_compact(lay, comp[s], keyset=keyset, skip_head_rows=True)}
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    committee = torch.empty(2, dtype=torch.int64, device=dev)
+
+    def leg_d(s):  # the C call: ConstraintChecker.check_keyset reads its result back, which a timed leg must not
+        rc = pkg.lib().blsw_r1cs_check_keyset(chk._r, keyset._ks, committee[0:].data_ptr(), committee[1:].data_ptr(), stream)
+        assert rc == 0, rc
+        return committee
+
+    legs["check_keyset"] = leg_d
+    ms = {k: [] for k in legs}
+    same = True
+    for rep_i in range(reps + 1):  # the first repetition warms up
+        s = rep_i % a.steps
+        outs = {}
+        for k, fn in legs.items():  # alternating: a, b, c, d, a, ...
+            with StepLimit(a.limit, "repetition %d of %s" % (rep_i, k)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                outs[k] = fn(s)
+                e1.record()
+                torch.cuda.synchronize()
+            if rep_i:
+                ms[k].append(e0.elapsed_time(e1))
+        same = same and torch.equal(outs["expand_then_check"], outs["check_compact"]) and torch.equal(outs["check_compact"], outs["check_compact_skip"])
+        same = same and bool((outs["check_compact"] < 0).all()) and outs["check_keyset"].tolist() == [-1, -1]
+    eng.close()
+    keyset.close()
+    out = {"metric": "r1cs_check_compact_keyset", "n": n, "n_keys": K, "steps": a.steps, "abi": pkg.lib().blsw_version(), "legs_agree_and_satisfied": same,
+           "n_constraints": int(mats["n_constraints"]), "head_rows": head_rows, "head_rows_share": round(head_rows / int(mats["n_constraints"]), 3),
+           "compact_bytes_per_instance": lay.total // n, "expanded_bytes_per_instance": int(mats["n_witness"]) * 48, "host_matrices_s": round(t_mats, 2)}
+    out.update({k: stats(v, n) for k, v in ms.items()})
+    del out["check_keyset"]["instances_per_s"]  # once per set, not per instance
+    for k in ("check_compact", "check_compact_skip"):  # every new leg against the route that existed before, never against each other
+        out[k + "_over_expand_then_check"] = round(out[k]["median_ms"] / out["expand_then_check"]["median_ms"], 3)
+    print(json.dumps(out))
+    if not same:
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--n", type=int, default=None, help="instances per batch / step: 1024, with --keyset 128 (the step of tools/agg_shared_rate.py)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--eval-n", type=int, default=64)
     ap.add_argument("--compact", action="store_true", help="expand_compact + check against check_compact, interleaved (see the module docstring)")
     ap.add_argument("--steps", type=int, default=2, help="--compact: distinct compact steps the calls rotate over")
     ap.add_argument("--eval-rows", type=int, default=20000, help="--compact: rows of the evaluate window (the pairing tail)")
+    ap.add_argument("--keyset", action="store_true", help="a shared-keys compact step: expand + check against the compact-keyset checks (see the module docstring)")
+    ap.add_argument("--keys", type=int, default=512, help="--keyset: keys of the committee")
+    ap.add_argument("--limit", type=float, default=240.0, help="--keyset: seconds per GPU step")
     a = ap.parse_args()
+    a.n = a.n or (128 if a.keyset else 1024)
     if a.compact:
         return compact_legs(a)
+    if a.keyset:
+        return keyset_legs(a)
     import torch
 
     pkg = importlib.import_module("bls-verify-gadget_amd")
