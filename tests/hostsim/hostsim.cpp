@@ -15,6 +15,7 @@
 #include "../../bls-verify-gadget_amd/csrc/prepare_vf.hpp"
 #include "../../bls-verify-gadget_amd/csrc/vpairing.hpp"
 #include "../../bls-verify-gadget_amd/csrc/r1cs_encode.hpp"
+#include "../devfield/ops.hpp"
 #include <array>
 
 using namespace blsw;
@@ -622,6 +623,47 @@ void hostsim_fp_inv_fermat(const uint64_t* a, uint64_t* r) {
     Fp z = fp_inv_fermat(load_fp(a));
     memcpy(r, z.l, 48);
 }
+// one operation of the field / tower table (tests/devfield/ops.hpp: the table tests/devfield/devfield.hip runs on the device) on one item:
+// a, b [12][6] u64 operand blocks, out [12][6] result elements (the operation's own count written, the rest untouched), wit: room for the
+// operation's witnesses, [n][6]. Returns the witness cursor after the operation, -1 for an unknown operation.
+int hostsim_field_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* wit) {
+    Fp fa[12], fb[12], fo[DEVFIELD_OUT_MAX];
+    for (int i = 0; i < 12; i++) {
+        fa[i] = load_fp(a + 6 * i);
+        fb[i] = load_fp(b + 6 * i);
+    }
+    Emitter e = {reinterpret_cast<uint32_t*>(wit), 0};
+    switch (op) {
+#define HOSTSIM_X_RUN(name, n_out, n_wit)                            \
+    case devfield::OP_##name:                                        \
+        devfield::FieldOp<devfield::OP_##name>::run(fa, fb, fo, e);  \
+        break;
+        DEVFIELD_OPS(HOSTSIM_X_RUN)
+#undef HOSTSIM_X_RUN
+        default:
+            return -1;
+    }
+    memcpy(out, fo, (size_t)devfield::op_n_out(op) * 48);
+    return (int)e.pos;
+}
+// the same over n items, with the arrays of devfield_run (one "lane" per item): out [n][12][6], wit [n][wcap][6], npos [n] the cursors
+int hostsim_field_op_batch(int op, uint64_t n, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* wit, uint32_t wcap, uint32_t* npos) {
+    if (devfield::op_n_out(op) < 0) return -1;
+    if ((int64_t)wcap < devfield::op_n_wit(op)) return -2;
+    for (uint64_t i = 0; i < n; i++) npos[i] = (uint32_t)hostsim_field_op(op, a + i * 72, b + i * 72, out + i * 72, wit + i * (uint64_t)wcap * 6);
+    return 0;
+}
+const char* hostsim_field_op_name(int op) {
+    static const char* const T[devfield::OP_COUNT] = {
+#define HOSTSIM_X_NAME(name, n_out, n_wit) #name,
+        DEVFIELD_OPS(HOSTSIM_X_NAME)
+#undef HOSTSIM_X_NAME
+    };
+    return (op >= 0 && op < devfield::OP_COUNT) ? T[op] : "";
+}
+int hostsim_field_op_count() { return devfield::OP_COUNT; }
+int hostsim_field_op_n_out(int op) { return devfield::op_n_out(op); }
+int hostsim_field_op_n_wit(int op) { return devfield::op_n_wit(op); }
 // the device R1CS evaluator's encoder (r1cs_encode.hpp: what blsw_r1cs_device_bytes / blsw_r1cs_create run). codes[m]: nnz[m] entry codes;
 // table: room for nnz[0] + nnz[1] + nnz[2] elements of 6 u64, *table_size written; blk: room for n_constraints + 1 block starts, *n_blk = the
 // number of blocks (blk[n_blk] = n_constraints). Returns encode()'s code, the outputs written only on BLSW_OK.

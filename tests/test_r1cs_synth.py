@@ -3,12 +3,12 @@ encoder's coefficient classes and block cut (csrc/r1cs_encode.hpp through hostsi
 through hostsim_r1cs_row: accumulator, class dispatch, redc14) against big integers, the big-integer reference against the independent host check
 hostsim_lib.r1cs_check, and fp.hpp's products and inversions against Python integers."""
 import importlib
-import random
 
 import numpy as np
 import pytest
 
 from tests import hostsim_lib, r1cs_synth as S
+from tests.field_edges import field_edge_values
 from tests.r1cs_synth import GEN, NEG, P, POS, R, R_INV, SMALL
 
 SHAPES = (1, 3)  # n_instance_vars
@@ -191,16 +191,6 @@ def test_reference_agrees_with_the_host_check(ni):
         n_slack += 1
         assert S.first_unsatisfied(sys, z, 0) == r == host(z), r
     assert n_slack >= (250 if ni == 1 else 100) and (ni == 3 or n_slack == sum(s is not None for s in sys["slack"]))
-
-
-def field_edge_values():
-    """110 values (a few of them equal: 2^384 is R, 2^392 - 1 is the value with all fourteen 28-bit limbs set), all below p"""
-    v = [0, 1, 2, P - 1, P - 2, R, R * R, (P + 1) // 2, (P - 1) // 2, sum(0xFFFFFFF << (28 * k) for k in range(14))]
-    for w, kmax in ((28, 14), (30, 13), (32, 13)):  # the limb widths of fp_mul (28), fp_inv (30) and fp_mul32 (32), up to and past their top limb
-        for k in range(1, kmax + 1):
-            v += [1 << (w * k), (1 << (w * k)) - 1]
-    rng = random.Random(0xF1E1D)
-    return [x % P for x in v] + [rng.randrange(P) for _ in range(20)]
 
 
 def test_field_micro_checks():
