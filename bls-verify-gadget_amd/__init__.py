@@ -133,6 +133,8 @@ def lib():
         L.blsw_sign_batch.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, u64, vp]
         L.blsw_verify_workspace_bytes.argtypes = [u64, u32, ctypes.POINTER(u64)]
         L.blsw_verify_batch.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
+        L.blsw_verify_groups_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_verify_groups_batch.argtypes = [vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, u64, vp]
         L.blsw_microbench.argtypes = [ctypes.c_int, u32, u32, ctypes.POINTER(ctypes.c_double)]
         L.blsw_fill_rate.argtypes = [vp, u64, u32, ctypes.POINTER(ctypes.c_double)]
         mi, mp = ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)
@@ -168,7 +170,7 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_engine_create_ex", "blsw_engine_destroy", "blsw_engine_submit", "blsw_engine_submit_bytes", "blsw_engine_submit_multi", "blsw_engine_submit_multi_compact", "blsw_engine_submit_aggregate", "blsw_engine_flush", "blsw_engine_submitted", "blsw_engine_launched", "blsw_engine_materialised", "blsw_engine_wait_step",
                     "blsw_engine_output_consumed", "blsw_engine_compact_bytes", "blsw_engine_submit_compact", "blsw_engine_submit_aggregate_compact", "blsw_engine_expand_compact", "blsw_engine_expand_stats", "blsw_witness_digest", "blsw_hash_to_g2_workspace_bytes", "blsw_hash_to_g2_batch",
                     "blsw_decode_batch", "blsw_layout_aggregate", "blsw_aggregate_workspace_bytes", "blsw_aggregate_verify_batch", "blsw_layout_multi",
-                    "blsw_verify_multi_workspace_bytes", "blsw_verify_multi_batch", "blsw_matrices_info", "blsw_matrices_fill", "blsw_sign_batch", "blsw_microbench", "blsw_fill_rate", "blsw_layout_io", "blsw_engine_submit_io", "blsw_verify_workspace_bytes", "blsw_verify_batch", "blsw_matrices_info_io", "blsw_matrices_fill_io",
+                    "blsw_verify_multi_workspace_bytes", "blsw_verify_multi_batch", "blsw_matrices_info", "blsw_matrices_fill", "blsw_sign_batch", "blsw_microbench", "blsw_fill_rate", "blsw_layout_io", "blsw_engine_submit_io", "blsw_verify_workspace_bytes", "blsw_verify_batch", "blsw_verify_groups_workspace_bytes", "blsw_verify_groups_batch", "blsw_matrices_info_io", "blsw_matrices_fill_io",
                     "blsw_layout_params", "blsw_matrices_info_params", "blsw_matrices_fill_params", "blsw_aggregate_points_workspace_bytes", "blsw_aggregate_points_batch",
                     "blsw_r1cs_device_bytes", "blsw_r1cs_create", "blsw_r1cs_destroy", "blsw_r1cs_check", "blsw_r1cs_evaluate", "blsw_layout_inputs",
                     "blsw_matrices_info_inputs", "blsw_matrices_fill_inputs", "blsw_layout_aggregate_inputs", "blsw_matrices_info_aggregate_inputs",
@@ -935,6 +937,70 @@ def verify_batch(pk48, msg, sig96, want_status=False):
                                  torch.cuda.current_stream(dev).cuda_stream)
     if rc:
         raise BlswError("blsw_verify_batch failed: %d" % rc)
+    return (res, status) if want_status else res
+
+
+def _header_define(name):
+    """an integer #define of include/blsw.h (the header is the one place such a number is written)"""
+    import re
+
+    text = open(os.path.join(HERE, "..", "include", "blsw.h")).read()
+    return int(re.search(r"^#define\s+%s\s+(\w+)" % name, text, flags=re.M).group(1), 0)
+
+
+VERIFY_GROUPS_CHUNK = _header_define("BLSW_VGROUP_CHUNK")  # pairs one six-lane team folds with shared squarings
+
+
+def _group_scalars(torch, n, dev):
+    """n fresh 64-bit coefficients from the operating system's generator, none of them zero"""
+    import secrets
+
+    import numpy as np
+
+    r = np.frombuffer(secrets.token_bytes(8 * n), dtype=np.uint64).copy()
+    r[r == 0] = 1
+    return torch.from_numpy(r.view(np.int64)).to(dev)
+
+
+def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False):
+    """Batch verification of GROUPS of triples with random coefficients (blsw_verify_groups_batch, include/blsw.h): group j is instances
+    [j * group, min(n, (j + 1) * group)) and its verdict is 1 iff every instance decodes (both statuses OK), every coefficient is non-zero and
+    prod_i e(r_i pk_i, H(m_i)) * e(-g1, sum_i r_i sig_i) == 1 — one final exponentiation per group instead of one per triple. uint8 cuda tensors as
+    verify_batch -> int32 [ceil(n / group)], optionally with the decode statuses [n, 2].
+    scalars: None draws n 64-bit coefficients from secrets.token_bytes on the host (zeros replaced by 1); a given int64 / uint64 cuda tensor [n] is
+    used as is — predictable coefficients are NOT sound (include/blsw.h, P4). The workspace is allocated per call (the caching allocator keeps it)."""
+    torch = _require_cuda()
+    n, msg_len = pk48.shape[0], msg.shape[1]
+    assert pk48.shape == (n, 48) and sig96.shape == (n, 96) and msg.shape[0] == n and pk48.is_contiguous() and sig96.is_contiguous() and msg.is_contiguous()
+    dev = pk48.device
+    if scalars is None:
+        scalars = _group_scalars(torch, n, dev)
+    assert scalars.shape == (n,) and scalars.element_size() == 8 and not scalars.is_floating_point() and scalars.is_contiguous() and scalars.device == dev
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_verify_groups_workspace_bytes(n, msg_len, group, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_verify_groups_workspace_bytes failed: %d" % rc)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    res = torch.empty((n + group - 1) // group, dtype=torch.int32, device=dev)
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    rc = lib().blsw_verify_groups_batch(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n, scalars.data_ptr(), group, res.data_ptr(),
+                                        status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_verify_groups_batch failed: %d" % rc)
+    return (res, status) if want_status else res
+
+
+def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=False):
+    """verify_batch through verify_groups: int32 [n] with the meaning of verify_batch. The instances of passing groups are 1; the instances of failing
+    groups are gathered, put through verify_batch and scattered back. ONE host synchronisation, to learn which groups failed. A batch in which most
+    groups hold a bad instance is slower this way than verify_batch: it pays for the groups and then for nearly the whole batch again."""
+    torch = _require_cuda()
+    n = pk48.shape[0]
+    gres, status = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True)
+    res = gres.repeat_interleave(group)[:n].contiguous()
+    bad = torch.nonzero(res == 0).flatten()  # the synchronisation
+    if bad.numel():
+        res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous())
     return (res, status) if want_status else res
 
 

@@ -1280,6 +1280,62 @@ int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8
     launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + off_ls), reinterpret_cast<Fp*>(base + off_lh), d_status, d_result, st);
     return hip_ok(hipGetLastError(), "launch");
 }
+// Groups of triples verified with the caller's coefficients (include/blsw.h, ABI 17; vgroups.hpp). Workspace: the step descriptor, the decoded points,
+// the scaled points, the group sums and flags, ONE set of per-instance lines, the per-group lines, the partial products, then the hash's carve.
+struct VerifyGroupsOffsets {
+    uint64_t pk, sig, p_scaled, s_scaled, sum, gflag, lines_h, lines_g, partials;
+};
+static_assert(BLSW_VGROUP_CHUNK >= 1 && BLSW_VGROUP_CHUNK <= 31, "a chunk's pairs and the group's own are the bits of one 32-bit mask");
+static uint64_t verify_groups_offsets(uint64_t n, uint32_t group, VerifyGroupsOffsets* f) {
+    const uint64_t G = (n + group - 1) / group;
+    const uint64_t eff = (uint64_t)group < n ? group : n, teams = G * ((eff + BLSW_VGROUP_CHUNK - 1) / BLSW_VGROUP_CHUNK);
+    uint64_t o = 256;  // the step descriptor
+    f->pk = o;
+    o = align_up(o + n * 96, 256);
+    f->sig = o;
+    o = align_up(o + n * 192, 256);
+    f->p_scaled = o;
+    o = align_up(o + 3 * n * sizeof(Fp), 256);
+    f->s_scaled = o;
+    o = align_up(o + 6 * n * sizeof(Fp), 256);
+    f->sum = o;
+    o = align_up(o + 4 * G * sizeof(Fp), 256);
+    f->gflag = o;
+    o = align_up(o + G * sizeof(int32_t), 256);
+    f->lines_h = o;
+    o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * n * sizeof(Fp), 256);
+    f->lines_g = o;
+    o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * G * sizeof(Fp), 256);
+    f->partials = o;
+    return align_up(o + teams * 12 * sizeof(Fp), 256);
+}
+int blsw_verify_groups_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t group, uint64_t* bytes) {
+    if (!bytes || n == 0 || n > 0x7fffffffu || msg_len > 65535 || group == 0 || group > 65535) return BLSW_ERR_ARG;
+    VerifyGroupsOffsets f;
+    *bytes = direct_values_bytes(n, msg_len, verify_groups_offsets(n, group, &f));
+    return BLSW_OK;
+}
+int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
+                             uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    if (!d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_scalars || group == 0 || group > 65535 || !d_group_result || !d_status ||
+        !d_workspace || msg_len > 65535)
+        return BLSW_ERR_ARG;
+    VerifyGroupsOffsets f;
+    const uint64_t off_ws = verify_groups_offsets(n, group, &f);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    uint64_t* pk_xy = reinterpret_cast<uint64_t*>(base + f.pk);
+    uint64_t* sig_xy = reinterpret_cast<uint64_t*>(base + f.sig);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    Group g;
+    if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
+    hipLaunchKernelGGL(k_decode, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, d_pk48, d_sig96, n, pk_xy, sig_xy, d_status);
+    launch_values_hash(g, st);
+    launch_verify_groups(n, group, BLSW_VGROUP_CHUNK, g.ws, pk_xy, sig_xy, d_status, d_scalars, reinterpret_cast<Fp*>(base + f.p_scaled), reinterpret_cast<Fp*>(base + f.s_scaled),
+                         reinterpret_cast<Fp*>(base + f.sum), reinterpret_cast<int32_t*>(base + f.gflag), reinterpret_cast<Fp*>(base + f.lines_h),
+                         reinterpret_cast<Fp*>(base + f.lines_g), reinterpret_cast<Fp*>(base + f.partials), d_group_result, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
 // BLS::sign + PublicKey::from(&sk) for a batch (bls.rs:411-425, 183-195). Workspace: blsw_hash_to_g2_workspace_bytes.
 int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
                     uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {

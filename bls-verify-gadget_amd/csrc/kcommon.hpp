@@ -692,6 +692,10 @@ void launch_pairing(const Group& g, const Modes& m, hipStream_t st);
 // blsw_verify_batch: projective lines of (sig, H(m)) then the six-lane value-only pairing check (k_team.hip, vpairing.hpp)
 void launch_verify_values(uint64_t n, const Workspace& ws, const uint64_t* pk_xy, const uint64_t* sig_xy, Fp* lines_sig, Fp* lines_h, const int32_t* status, int32_t* result,
                           hipStream_t st);
+// blsw_verify_groups_batch: scale, group sums, one line chain per instance and per group, chunked fold, one final exponentiation per group
+// (k_vgroups.hip, vgroups.hpp). `chunk` <= 31 pairs per team.
+void launch_verify_groups(uint64_t n, uint32_t group, uint32_t chunk, const Workspace& ws, const uint64_t* pk_xy, const uint64_t* sig_xy, const int32_t* status, const uint64_t* scalars,
+                          Fp* p_scaled, Fp* s_scaled, Fp* sum_xy, int32_t* gflag, Fp* lines_h, Fp* lines_g, Fp* partials, int32_t* result, hipStream_t st);
 
 }  // namespace blsw
 

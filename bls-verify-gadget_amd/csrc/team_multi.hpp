@@ -35,6 +35,28 @@ struct TeamLanesValues : TeamLanes<CoeffStrided> {
     }
 };
 
+// blsw_verify_groups_batch (vgroups.hpp): one pair per step and `count` instance pairs per chunk, the group's own pair (-g1, S_g) behind them in the
+// group's first chunk. `mask` bit p = pair p of the chunk is folded (the same on the six lanes); a cleared bit is a skipped pair.
+struct TeamLanesGroups : TeamLanes<CoeffStrided> {
+    const Fp* lines_h;   // [BLSW_VLINE_ROWS][n]
+    const Fp* lines_g;   // [BLSW_VLINE_ROWS][n_groups]
+    const Fp* partials;  // [teams][6] Fp2
+    uint64_t n, n_groups, first, grp;
+    uint32_t count, mask;
+    BLSW_TEAM_DEV Reg one() const { return j == 0 ? fp2_one() : fp2_zero(); }
+    BLSW_TEAM_DEV bool load_pair(uint64_t p, uint32_t k) {
+        const uint32_t rel = (uint32_t)(p - first);
+        if (!((mask >> rel) & 1u)) return false;
+        if (active) team_load_pair_lines_lane(j, slots, rel < count ? CoeffStrided{const_cast<Fp*>(lines_h) + p, n} : CoeffStrided{const_cast<Fp*>(lines_g) + grp, n_groups}, k);
+        team_sync();
+        return true;
+    }
+    BLSW_TEAM_DEV Reg load_partial(uint64_t idx) const {
+        const Fp* p = partials + (idx * 6 + j) * 2;
+        return active ? Fp2{ld_fp(p), ld_fp(p + 1)} : fp2_zero();
+    }
+};
+
 // single-key circuit with ParametersVar allocated as witnesses (team_miller_pv): both pairs go through the pair slots
 struct TeamLanesPv : TeamLanes<CoeffStrided> {
     Fp pkx, pky;  // lane 5 / lane 4 hold prepare_g1(pk)

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BLSW_ABI_VERSION 16
+#define BLSW_ABI_VERSION 17
 
 #define BLSW_OK 0
 #define BLSW_ERR_ARG 1
@@ -562,6 +562,35 @@ int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg
 int blsw_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes);
 int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result, int32_t* d_status,
                       void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* ABI 17: batch verification of GROUPS of triples with random coefficients, the form every consensus client verifies in (blst's
+ * verify_multiple_aggregate_signatures). Group j is instances [j * group, min(n, (j + 1) * group)): ceil(n / group) groups, the last one may be short,
+ * group > n gives one group. With the caller's 64-bit coefficients r_i = d_scalars[i]
+ *     d_group_result[j] = 1  iff  every instance of the group has both statuses BLSW_ST_OK and r_i != 0,  and
+ *                                 prod_i e(r_i pk_i, H(msg_i)) * e(-g1, sum_i r_i sig_i) == 1
+ * — one final exponentiation per group, one line chain per instance, and the squarings of the Miller loop shared by the BLSW_VGROUP_CHUNK pairs one
+ * six-lane team folds. It fails closed: a zero coefficient makes its group 0; an instance whose status is not OK contributes nothing to the product or
+ * the sum (its points are zeros) and makes its group 0. d_status [n][2] is exactly what blsw_verify_batch writes. The library reads no entropy, as it
+ * reads no environment: the coefficients are the caller's. What callers (and the tests) can rest on:
+ *   P1  all instances of a group valid                              -> 1 for ANY non-zero coefficients.
+ *   P2  exactly one instance fails its pairing equation, all statuses OK, all coefficients non-zero
+ *                                                                   -> 0 for ANY such coefficients: GT has prime order r > 2^64, so e_bad^(r_bad) != 1.
+ *   P3  group == 1                                                  -> the verdict of blsw_verify_batch, for any non-zero coefficient.
+ *   P4  two or more invalid instances: the group passes only if the coefficients satisfy one linear relation mod r. Independent, uniform,
+ *       unpredictable 64-bit coefficients chosen AFTER the inputs are fixed accept a bad group with probability <= 2^-64.
+ * The subgroup checks of the decode are what make this sound: P2 and P4 argue in groups of prime order r, and a point outside them could carry a
+ * small-order component that a coefficient kills. Predictable coefficients are not sound: with EQUAL coefficients the two invalid triples
+ * (pk, m1, sig2) and (pk, m2, sig1), sig_k = sk * H(m_k), pass as a group — their signatures are swapped, and the sum does not see it.
+ *   BLSW_ERR_ARG before any HIP call: group == 0 or > 65535, n == 0 or > 0x7fffffff, msg_len > 65535, a NULL among d_pk48, d_sig96, d_scalars,
+ *   d_group_result, d_status, d_workspace, or d_msg == NULL with msg_len != 0. BLSW_ERR_WORKSPACE for a workspace below
+ *   blsw_verify_groups_workspace_bytes(n, msg_len, group) — smaller than blsw_verify_workspace_bytes: it holds one set of lines, not two.
+ *   Asynchronous on `stream` after one synchronising descriptor copy, as blsw_verify_batch. */
+#ifndef BLSW_VGROUP_CHUNK
+#define BLSW_VGROUP_CHUNK 8 /* pairs one six-lane team folds with shared squarings (<= 31). Provisional, not measured: at n = 65 536 it launches 8 192 teams, under the 10 240 resident at once */
+#endif
+int blsw_verify_groups_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t group, uint64_t* bytes);
+int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
+                             uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* Device micro-benchmarks that give the VALU roofline its MEASURED denominator:
  * which = 0: v_mad_u64_u32 rate (32x32+64 multiply-adds per second, all CUs); 1: Fp Montgomery products per second;

@@ -22,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <random>
 #include <vector>
 
 #include "blsw.h"
@@ -738,6 +739,81 @@ struct BLS {
         }
         std::vector<bool> out(n);
         for (size_t i = 0; i < n; i++) out[i] = r[i] == 1;
+        return out;
+    }
+    // n fresh 64-bit coefficients from the operating system's generator, none of them zero (what verify_groups draws when given none)
+    static std::vector<uint64_t> group_scalars(size_t n) {
+        std::random_device rd;
+        std::vector<uint64_t> r(n);
+        for (auto& v : r) {
+            v = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
+            if (v == 0) v = 1;
+        }
+        return r;
+    }
+    // Groups of triples verified with random coefficients (blsw_verify_groups_batch, include/blsw.h): verdict j is for triples
+    // [j * group, min(n, (j + 1) * group)) — true iff every triple decodes, every coefficient is non-zero and the group's product of pairings is one.
+    // scalars: empty draws group_scalars(n); given ones are used as they are, and predictable ones are NOT sound (include/blsw.h, P4).
+    static std::vector<bool> verify_groups(const Parameters&, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
+                                           const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
+                                           std::vector<int32_t>* status = nullptr) {
+        const size_t n = pks.size();
+        if (n == 0 || messages.size() != n || sigs.size() != n || group == 0) throw Error("BLS::verify_groups: one message and one signature per key", BLSW_ERR_ARG);
+        if (scalars.empty()) scalars = group_scalars(n);
+        if (scalars.size() != n) throw Error("BLS::verify_groups: one coefficient per triple", BLSW_ERR_ARG);
+        const uint32_t msg_len = (uint32_t)messages[0].size();
+        std::vector<uint8_t> pk(n * 48), sg(n * 96), msg(n * (size_t)msg_len);
+        for (size_t i = 0; i < n; i++) {
+            if (messages[i].size() != msg_len) throw Error("BLS::verify_groups: messages of one length per batch", BLSW_ERR_ARG);
+            std::memcpy(&pk[48 * i], pks[i].bytes.data(), 48);
+            std::memcpy(&sg[96 * i], sigs[i].bytes.data(), 96);
+            if (msg_len) std::memcpy(&msg[(size_t)msg_len * i], messages[i].data(), msg_len);
+        }
+        const size_t n_groups = (n + group - 1) / group;
+        uint64_t bytes = 0;
+        check(blsw_verify_groups_workspace_bytes(n, msg_len, group, &bytes), "blsw_verify_groups_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_pk(pk.size()), d_sg(sg.size()), d_msg(msg.size()), d_sc(n * 8), d_st(n * 8), d_res(n_groups * 4);
+        d_pk.upload(pk.data(), pk.size());
+        d_sg.upload(sg.data(), sg.size());
+        d_sc.upload(scalars.data(), n * 8);
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        check(blsw_verify_groups_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
+                                       static_cast<const uint64_t*>(d_sc.get()), group, static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes,
+                                       nullptr),
+              "blsw_verify_groups_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n_groups);
+        d_res.download(r.data(), n_groups * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
+        }
+        std::vector<bool> out(n_groups);
+        for (size_t j = 0; j < n_groups; j++) out[j] = r[j] == 1;
+        return out;
+    }
+    // BLS::verify through verify_groups: the triples of passing groups are true, those of failing groups go through verify once more. A batch in which
+    // most groups hold a bad triple is slower this way than verify.
+    static std::vector<bool> verify_grouped(const Parameters& params, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
+                                            const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
+                                            std::vector<int32_t>* status = nullptr) {
+        const std::vector<bool> g = verify_groups(params, pks, messages, sigs, group, std::move(scalars), status);
+        const size_t n = pks.size();
+        std::vector<bool> out(n, true);
+        std::vector<size_t> idx;
+        for (size_t i = 0; i < n; i++)
+            if (!g[i / group]) idx.push_back(i);
+        if (idx.empty()) return out;
+        std::vector<PublicKey> p2;
+        std::vector<std::vector<uint8_t>> m2;
+        std::vector<Signature> s2;
+        for (size_t i : idx) {
+            p2.push_back(pks[i]);
+            m2.push_back(messages[i]);
+            s2.push_back(sigs[i]);
+        }
+        const std::vector<bool> r = verify(params, p2, m2, s2);
+        for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
         return out;
     }
 };
