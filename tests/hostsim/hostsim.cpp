@@ -16,6 +16,7 @@
 #include "../../bls-verify-gadget_amd/csrc/vpairing.hpp"
 #include "../../bls-verify-gadget_amd/csrc/r1cs_encode.hpp"
 #include "../devfield/ops.hpp"
+#include "../devteam/ops.hpp"
 #include <array>
 
 using namespace blsw;
@@ -128,6 +129,21 @@ struct TeamHost {
         for (uint32_t j = 0; j < 6; j++) res = team_is_one_tree(j, b, e_one);
         return res;
     }
+    // what the operation table of tests/devteam/ops.hpp adds to the interface: operand blocks in, the six coefficients of a result out
+    Fp* out = nullptr;  // [12]
+    void set_coeffs(const Fp* c) { coeff_sig = coeff_h = CoeffLinear{const_cast<Fp*>(c)}; }
+    void load_pair_lines(uint32_t k) {
+        for (uint32_t j = 0; j < 6; j++) team_load_pair_lines_lane(j, slots, coeff_h, k);
+    }
+    Reg ld(const Fp* p) const {
+        Reg r;
+        for (uint32_t j = 0; j < 6; j++) r[j] = {p[2 * j], p[2 * j + 1]};
+        return r;
+    }
+    void st(const Reg& r) {
+        for (uint32_t j = 0; j < 6; j++) devteam::st2(out + 2 * j, r[j]);
+    }
+    void st_flag(bool v) { devteam::st_verdict(out, v); }
 };
 static int g_use_team = 0;
 static int g_cofactor_par = 0;  // 1: clear_cofactor2 through cofactor_par.hpp (chunks in the order 2, 0, 1, then the join); 2: cofactor_vf.hpp
@@ -664,6 +680,57 @@ const char* hostsim_field_op_name(int op) {
 int hostsim_field_op_count() { return devfield::OP_COUNT; }
 int hostsim_field_op_n_out(int op) { return devfield::op_n_out(op); }
 int hostsim_field_op_n_wit(int op) { return devfield::op_n_wit(op); }
+// one entry of the team operation table (tests/devteam/ops.hpp: the table tests/devteam/devteam.hip runs on the device) over n items. form 0: the
+// single-lane statement; 1 / 2: the team form through exec / exec_hot on the looped team above (one text on the host). a, b, c [n][12][6] u64 operand
+// blocks; out [n][12][6] the six coefficients of the result; wit [n][wcap][6]; npos [n] the cursor after the entry (the team's own cursor, which does
+// not pass the entry's tail). Returns 0, -1 for an unknown entry or form, -2 when wcap is below the entry's witness count.
+int hostsim_team_op(int form, int op, uint64_t n, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, uint64_t* wit, uint32_t wcap, uint32_t* npos) {
+    const int64_t n_wit = devteam::op_n_wit(op, devteam::NwTables());
+    if (n_wit < 0 || form < 0 || form > 2) return -1;
+    if ((int64_t)wcap < n_wit) return -2;
+    for (uint64_t i = 0; i < n; i++) {
+        Fp fa[12], fb[12], fc[12], fo[12];
+        for (int k = 0; k < 12; k++) {
+            fa[k] = load_fp(a + i * 72 + 6 * k);
+            fb[k] = load_fp(b + i * 72 + 6 * k);
+            fc[k] = load_fp(c + i * 72 + 6 * k);
+        }
+        Emitter e = {reinterpret_cast<uint32_t*>(wit + i * (uint64_t)wcap * 6), 0};
+        TeamHost t;
+        memset(t.slots, 0, sizeof(t.slots));
+        t.e = e;
+        t.out = fo;
+        t.pkx = t.pky = fp_zero();
+        switch (op) {
+#define HOSTSIM_X_TEAM(name, dual, g2, w, tail)                                              \
+    case devteam::OP_##name:                                                                 \
+        if (form == 0)                                                                       \
+            devteam::TeamEntry<devteam::OP_##name>::single(fa, fb, fc, fo, e);               \
+        else if (form == 1)                                                                  \
+            devteam::TeamEntry<devteam::OP_##name>::team<false>(t, fa, fb, fc, 0);           \
+        else                                                                                 \
+            devteam::TeamEntry<devteam::OP_##name>::team<true>(t, fa, fb, fc, 0);            \
+        break;
+            DEVTEAM_OPS(HOSTSIM_X_TEAM)
+#undef HOSTSIM_X_TEAM
+        }
+        memcpy(out + i * 72, fo, sizeof(fo));
+        npos[i] = form == 0 ? e.pos : t.e.pos;
+    }
+    return 0;
+}
+const char* hostsim_team_op_name(int op) {
+    static const char* const T[devteam::OP_COUNT] = {
+#define HOSTSIM_X_TNAME(name, dual, g2, w, tail) #name,
+        DEVTEAM_OPS(HOSTSIM_X_TNAME)
+#undef HOSTSIM_X_TNAME
+    };
+    return (op >= 0 && op < devteam::OP_COUNT) ? T[op] : "";
+}
+int hostsim_team_op_count() { return devteam::OP_COUNT; }
+int hostsim_team_op_n_wit(int op) { return (int)devteam::op_n_wit(op, devteam::NwTables()); }
+int hostsim_team_op_tail(int op) { return (int)devteam::op_tail(op, devteam::NwTables()); }
+int hostsim_team_op_dual(int op) { return devteam::op_dual(op); }
 // the device R1CS evaluator's encoder (r1cs_encode.hpp: what blsw_r1cs_device_bytes / blsw_r1cs_create run). codes[m]: nnz[m] entry codes;
 // table: room for nnz[0] + nnz[1] + nnz[2] elements of 6 u64, *table_size written; blk: room for n_constraints + 1 block starts, *n_blk = the
 // number of blocks (blk[n_blk] = n_constraints). Returns encode()'s code, the outputs written only on BLSW_OK.

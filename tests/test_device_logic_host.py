@@ -383,6 +383,14 @@ def test_team_table_invariants():
         for o in op.out:
             o.lists()
             assert all(slot in written or slot < gen.P0 or slot >= gen.X0 for slot in o.d), op.name
+        if op.name in ("G2DBL", "G2ADD"):
+            # k_g2_alloc_team sizes its LDS file by these two tables: TS_P + 12 slots per team
+            named = set(written) - {0xFF}
+            for t in op.tasks:
+                named |= set(t["a"].d) | set(t["b"].d)
+            for o in op.out:
+                named |= set(o.d)
+            assert named and max(named) < gen.P0 + 12, "%s names slot %d: beyond the slot file of k_g2_alloc_team" % (op.name, max(named))
 
 
 def test_value_only_hash_to_g2_device_logic(oracle):
