@@ -17,6 +17,7 @@
 #include "../../bls-verify-gadget_amd/csrc/r1cs_encode.hpp"
 #include "../devfield/ops.hpp"
 #include "../devteam/ops.hpp"
+#include "../devcurve/ops.hpp"
 #include <array>
 
 using namespace blsw;
@@ -731,6 +732,49 @@ int hostsim_team_op_count() { return devteam::OP_COUNT; }
 int hostsim_team_op_n_wit(int op) { return (int)devteam::op_n_wit(op, devteam::NwTables()); }
 int hostsim_team_op_tail(int op) { return (int)devteam::op_tail(op, devteam::NwTables()); }
 int hostsim_team_op_dual(int op) { return devteam::op_dual(op); }
+// one operation of the curve table (tests/devcurve/ops.hpp: the table tests/devcurve/devcurve.hip runs on the device) on one item, with the
+// arrays of hostsim_field_op; the PARK of v_clear_cofactor and v_g2_mul_gls is an array. Returns the witness cursor after the operation, -1 for an
+// unknown operation.
+int hostsim_curve_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* wit) {
+    Fp fa[12], fb[12], fo[DEVCURVE_OUT_MAX];
+    for (int i = 0; i < 12; i++) {
+        fa[i] = load_fp(a + 6 * i);
+        fb[i] = load_fp(b + 6 * i);
+    }
+    Jac2 park[DEVCURVE_PARK_SLOTS];
+    Emitter e = {reinterpret_cast<uint32_t*>(wit), 0};
+    switch (op) {
+#define HOSTSIM_X_CRUN(name, n_out, n_wit, quad)                                      \
+    case devcurve::OP_##name:                                                        \
+        devcurve::CurveOp<devcurve::OP_##name>::run(fa, fb, fo, e, ParkHost{park});  \
+        break;
+        DEVCURVE_OPS(HOSTSIM_X_CRUN)
+#undef HOSTSIM_X_CRUN
+        default:
+            return -1;
+    }
+    memcpy(out, fo, (size_t)devcurve::op_n_out(op) * 48);
+    return (int)e.pos;
+}
+// the same over n items, with the arrays of devcurve_run (one "lane" per item): out [n][12][6], wit [n][wcap][6], npos [n] the cursors
+int hostsim_curve_op_batch(int op, uint64_t n, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* wit, uint32_t wcap, uint32_t* npos) {
+    if (devcurve::op_n_out(op) < 0) return -1;
+    if ((int64_t)wcap < devcurve::op_n_wit(op)) return -2;
+    for (uint64_t i = 0; i < n; i++) npos[i] = (uint32_t)hostsim_curve_op(op, a + i * 72, b + i * 72, out + i * 72, wit + i * (uint64_t)wcap * 6);
+    return 0;
+}
+const char* hostsim_curve_op_name(int op) {
+    static const char* const T[devcurve::OP_COUNT] = {
+#define HOSTSIM_X_CNAME(name, n_out, n_wit, quad) #name,
+        DEVCURVE_OPS(HOSTSIM_X_CNAME)
+#undef HOSTSIM_X_CNAME
+    };
+    return (op >= 0 && op < devcurve::OP_COUNT) ? T[op] : "";
+}
+int hostsim_curve_op_count() { return devcurve::OP_COUNT; }
+int hostsim_curve_op_n_out(int op) { return devcurve::op_n_out(op); }
+int hostsim_curve_op_n_wit(int op) { return devcurve::op_n_wit(op); }
+int hostsim_curve_op_quad(int op) { return devcurve::op_quad(op); }
 // the device R1CS evaluator's encoder (r1cs_encode.hpp: what blsw_r1cs_device_bytes / blsw_r1cs_create run). codes[m]: nnz[m] entry codes;
 // table: room for nnz[0] + nnz[1] + nnz[2] elements of 6 u64, *table_size written; blk: room for n_constraints + 1 block starts, *n_blk = the
 // number of blocks (blk[n_blk] = n_constraints). Returns encode()'s code, the outputs written only on BLSW_OK.
