@@ -817,4 +817,23 @@ void hostsim_r1cs_row(const uint32_t* col, const uint32_t* code, uint64_t count,
     const Fp r = r1cs::redc14(x);
     memcpy(out, r.l, 48);
 }
+// sha.hpp's host BitSink alone, on the script tests/devstream/devstream.hip's k_devstream_sink runs on the device: entry i = (op, n), op 0 =
+// push(data[i], n), op 1 = push32(data[i]); one flush at the end. words [cap] receives the stream; returns the word count (widx), or -1 when the
+// stream does not fit; *nbits = the sink's bit count.
+int64_t hostsim_sink_script(const uint32_t* script, uint32_t n_ops, const uint32_t* data, uint32_t* words, uint64_t cap, uint64_t* nbits) {
+    uint64_t need = 0;
+    for (uint32_t i = 0; i < n_ops; i++) need += script[2 * i] == 0 ? script[2 * i + 1] : 32;
+    if ((need + 31) / 32 > cap) return -1;
+    BitSink s;
+    s.init(words, 1);
+    for (uint32_t i = 0; i < n_ops; i++) {
+        if (script[2 * i] == 0)
+            s.push(data[i], script[2 * i + 1]);
+        else
+            s.push32(data[i]);
+    }
+    s.flush();
+    *nbits = s.nbits;
+    return (int64_t)s.widx;
+}
 }

@@ -19,7 +19,12 @@ ORACLE_TO_ABI = {
 }
 
 
-@pytest.mark.parametrize("msg_len", [0, 3, 32, 55, 120])
+# msg' of expand_message is 111 bytes longer than the message (sha.hpp: total = msg_len + 111), so its SHA-256 block count (msg_len + 183) / 64 changes
+# at 8 / 9, 72 / 73, ...; the 0x80 byte opens a block of its own at msg_len = 17 (mod 64), and the two lib_str bytes straddle a block at 63 (mod 64)
+BLOCK_BORDER_LENGTHS = [8, 9, 16, 17, 18, 62, 63, 64, 65, 72, 73]
+
+
+@pytest.mark.parametrize("msg_len", [0, 3, 32, 55, 120] + BLOCK_BORDER_LENGTHS)
 def test_layout_matches_oracle_trace(oracle, msg_len):
     marks, n_wit, n_cons = oracle.layout(msg_len)
     lay = hostsim_lib.layout(msg_len)
@@ -93,7 +98,7 @@ def test_synthetic_and_edge_cases(oracle):
     _check(oracle, zero_pk, msg[0].tobytes(), sig[0])
 
 
-@pytest.mark.parametrize("msg", [b"", b"abc", b"x" * 119])
+@pytest.mark.parametrize("msg", [b"", b"abc", b"x" * 119] + [bytes((7 * i + n) & 0xFF for i in range(n)) for n in BLOCK_BORDER_LENGTHS], ids=lambda m: "len%d" % len(m) if len(m) in BLOCK_BORDER_LENGTHS else None)  # (the three earlier cases keep their ids)
 def test_other_message_lengths(oracle, msg):
     pk, _, sig, _ = synth.make_batch(oracle, 16)
     _check(oracle, pk[1], msg, sig[1])

@@ -204,11 +204,14 @@ def test_other_message_lengths(pkg, oracle, msg_len):
     _compare(oracle, pk, msg.reshape(2, msg_len), sig, got, w, range(2))
 
 
-@pytest.mark.parametrize("msg_len", [55, 56, 119, 120, 251])
+@pytest.mark.parametrize("msg_len", [55, 56, 119, 120, 251, 8, 9, 17, 63, 73])
 def test_engine_grouped_padding_boundary_lengths(pkg, oracle, msg_len):
     """The witness path on long and block-boundary messages through the GROUPED engine (staging, streamed expansion and
-    placement): msg' = Z_pad || msg || ... of expand_message (hasher.rs:110-173) crosses SHA-256 padding boundaries at 55 / 56
-    and 119 / 120 bytes, and 251 bytes is the longest of the reference's own strings (hasher.rs:1006-1012). Two steps of 70
+    placement). msg' = Z_pad || msg || ... of expand_message (hasher.rs:110-173) is 111 bytes longer than the message (sha.hpp: total =
+    msg_len + 111), so its SHA-256 block count is (msg_len + 183) / 64 and changes at 8 / 9, 72 / 73, 136 / 137 and 200 / 201 bytes (NOT at
+    55 / 56 and 119 / 120, which are the borders of a bare message and stay here as ordinary lengths); the 0x80 byte opens a block of its
+    own at msg_len = 17 (mod 64), and the two lib_str witness bytes straddle a block at msg_len = 63 (mod 64). sha_bits, and with it the
+    tail shape of the expansion, changes exactly there. 251 bytes is the longest of the reference's own strings (hasher.rs:1006-1012). Two steps of 70
     instances fused into one group (140 lanes: two full waves and a ragged one); valid and tampered signatures; every
     fifth vector and the ragged tail, element by element, against the oracle."""
     import torch
