@@ -39,6 +39,18 @@ BLSW_FN Proj<OpsFp> chain_g1_alloc_only(Emitter e_alloc, const Fp& pkx, const Fp
         acc = jac1_dbl(acc);
         if (bit_of(H1INV, i)) acc = jac1_add_mixed(acc, pkx, pky);
     }
+    // jac1_add_mixed has no branches: an accumulator that is O or +-pk on the way (a key of order 3 or 11: the entry points make no subgroup
+    // check) leaves Z = 0 from there on. One test finds it; that lane walks the ladder again by the full group law. A product that IS O is
+    // allocated as (0, 1, 0), as arkworks does (no key but the identity gives one: h^-1 mod r is a unit modulo every prime factor of h).
+    if (fp_is_zero(acc.z) && !inf) {
+        acc = {pkx, pky, fp_one()};
+#pragma unroll 1
+        for (int i = BLSW_H1INV_NBITS - 2; i >= 0; i--) {
+            acc = jac1_dbl(acc);
+            if (bit_of(H1INV, i)) acc = jac1_add_mixed_full(acc, pkx, pky);
+        }
+        inf = fp_is_zero(acc.z);
+    }
     Fp zi = fp_inv(acc.z);
     Fp zi2 = fp_sqr(zi);
     Fp px = fp_mul(acc.x, zi2), py = fp_mul(acc.y, fp_mul(zi2, zi));
@@ -428,16 +440,21 @@ BLSW_HD void prepare_add_step(Emitter& e, const Fp2& qx, const Fp2& qy, Fp2& rx,
     out.st(4 * k + 2, f.c0);
     out.st(4 * k + 3, f.c1);
 }
+// the 68 steps after to_affine, from the affine point (qx, qy), the cursor behind to_affine's witnesses
 template <class C>
-BLSW_FN void chain_prepare_g2(Emitter e, const Proj<OpsFp2>& q_, const C& out) {
-    Aff2Inf q = g2_to_affine_w(e, q_);
-    Fp2 rx = q.x, ry = q.y;
+BLSW_FN void chain_prepare_g2_steps(Emitter e, const Fp2& qx, const Fp2& qy, const C& out) {
+    Fp2 rx = qx, ry = qy;
     uint32_t k = 0;
 #pragma unroll 1
     for (int i = 62; i >= 0; i--) {
         prepare_dbl_step(e, rx, ry, fp2_inv(ry), out, k++);
-        if ((BLSW_X_ABS >> i) & 1) prepare_add_step(e, q.x, q.y, rx, ry, fp2_inv(fp2_sub(q.x, rx)), out, k++);
+        if ((BLSW_X_ABS >> i) & 1) prepare_add_step(e, qx, qy, rx, ry, fp2_inv(fp2_sub(qx, rx)), out, k++);
     }
+}
+template <class C>
+BLSW_FN void chain_prepare_g2(Emitter e, const Proj<OpsFp2>& q_, const C& out) {
+    Aff2Inf q = g2_to_affine_w(e, q_);
+    chain_prepare_g2_steps(e, q.x, q.y, out);
 }
 
 // ------------------------------------------------------------------------------------------------ pairing

@@ -242,5 +242,15 @@ BLSW_FN Jac1 jac1_add_mixed(const Jac1& p, const Fp& qx, const Fp& qy) {
     Fp z3 = fp_sub(fp_sub(fp_sqr(fp_add(p.z, h)), z1z1), hh);
     return {x3, y3, z3};
 }
+// the same for any p: the identity (Z = 0) gives q, p = q the doubling, p = -q the identity (1, 1, 0). chain_g1_alloc_only's second walk.
+BLSW_FN Jac1 jac1_add_mixed_full(const Jac1& p, const Fp& qx, const Fp& qy) {
+    if (fp_is_zero(p.z)) return {qx, qy, fp_one()};
+    Fp z1z1 = fp_sqr(p.z);
+    if (fp_is_zero(fp_sub(fp_mul(qx, z1z1), p.x))) {
+        if (fp_is_zero(fp_sub(fp_mul(fp_mul(qy, p.z), z1z1), p.y))) return jac1_dbl(p);
+        return {fp_one(), fp_one(), fp_zero()};
+    }
+    return jac1_add_mixed(p, qx, qy);
+}
 
 }  // namespace blsw

@@ -8,8 +8,14 @@
 // 1 / (q.x - x) = 2 Z^3 / Z' for an addition — and runs the step's statements (chains.hpp: prepare_dbl_step / prepare_add_step) at the step's
 // place in the segment. Field elements are canonical residues: the same bytes as the affine chain.
 // Serial work: 63 x 19 + 5 x 32 products + 2 inversions (to_affine, last Z) instead of 68 x ~48 with 69 inversions.
-// Degenerate inputs: the identity (to_affine gives (0, 0), every Z, inverse and slope 0) runs as the circuit does; a point of order two
-// inside the chain or r = +-q at an addition (impossible for points of prime order r) would differ from the circuit's zero-hint arithmetic.
+// Degenerate inputs: the identity (to_affine gives (0, 0), every Z, inverse and slope 0) runs as the circuit does. A point whose chain meets
+// r = +-q at an addition (or a point of order two) is impossible for H(m), which has prime order r, but not for a caller's signature: the witness
+// entry points make no subgroup check, and a point of order 13 on the twist reaches r = -q at the second addition (the prefixes of |x| run 1, 3,
+// 6, 12). There the circuit's zero-hint arithmetic goes on with slope 0 on a pair that is no curve point, which Jacobian values cannot follow.
+// Such a step makes its Z' = 2 Z H (or 2 Y Z) zero and every later Z with it, so "the last Z is 0 and the input is not the identity" finds the
+// case with one test per point; that lane then runs the circuit's affine steps itself (chain_prepare_g2_steps), leaves each step's line
+// coefficients in ST(k) and marks every ZI(k) of the point with BLSW_PREPV_DEGENERATE, on which the step lanes copy the coefficients out and
+// return. (tests/test_chain_edges.py, test_chain_edges_gpu.py)
 #pragma once
 #include "cofactor_vf.hpp"
 
@@ -44,6 +50,25 @@ static_assert(prepv_plan().total == 1096, "prepare segment: the plan must count 
 #define BLSW_PREPV_ST(k) (4u + 10u * (uint32_t)(k))
 #define BLSW_PREPV_ZI(k) (4u + 10u * BLSW_PREPV_STEPS + 2u * (uint32_t)(k))
 #define BLSW_PREPV_ELEMS (4u + 10u * BLSW_PREPV_STEPS + 2u * (BLSW_PREPV_STEPS + 1))
+// the top limb of ZI(k).c1 of a point whose steps phase 1 has written itself: above p's top limb, so no residue has it
+#define BLSW_PREPV_DEGENERATE 0xFFFFFFFFu
+
+// the line coefficients of a degenerate point travel through its scratch: step k's four go to ST(k) .. ST(k) + 3, where its step lane finds them
+template <class S>
+struct PrepvCoeffScr {
+    const S& scr;
+    BLSW_HD void st(uint32_t idx, const Fp& v) const { scr.st(BLSW_PREPV_ST(idx >> 2) + (idx & 3u), v); }
+};
+// the degenerate point's lane (or quad): the circuit's affine steps, and the mark on every ZI(k). Out of line in every compilation: the chain
+// of an ordinary point keeps its registers.
+template <class S>
+BLSW_HD_NOINLINE void prepv_degenerate(Emitter e, const Fp2& qx, const Fp2& qy, const S& scr) {
+    chain_prepare_g2_steps(e, qx, qy, PrepvCoeffScr<S>{scr});
+    Fp mark = fp_zero();
+    mark.l[11] = BLSW_PREPV_DEGENERATE;
+#pragma unroll 1
+    for (uint32_t k = 0; k <= BLSW_PREPV_STEPS; k++) cofv_st2(scr, BLSW_PREPV_ZI(k), Fp2{fp_zero(), mark});
+}
 
 // ---- phase 1 (one lane, or one quad, per point): to_affine with its witnesses, then the chain of points as values
 template <class S>
@@ -77,6 +102,10 @@ BLSW_FN void prepv_chain(Emitter e, const Proj<OpsFp2>& q_, const S& scr) {
             Y = y3;
         }
     }
+    if (fp2_is_zero(Z) && !q.infinity) {  // a degenerate step on the way: the circuit's own statements, and no step lane for this point
+        prepv_degenerate(e, q.x, q.y, scr);
+        return;
+    }
     Fp2 zi = fp2_inv_inl(Z);
     cofv_st2(scr, BLSW_PREPV_ZI(BLSW_PREPV_STEPS), zi);
 #pragma unroll 1
@@ -94,6 +123,13 @@ BLSW_FN void prepv_step_w(Emitter e, uint32_t k, const S& scr, const C& out) {
     constexpr PrepvPlan plan = prepv_plan();
     const Fp2 X = cofv_ld2(scr, BLSW_PREPV_ST(k)), Y = cofv_ld2(scr, BLSW_PREPV_ST(k) + 2), Z = cofv_ld2(scr, BLSW_PREPV_ST(k) + 4);
     const Fp2 zi = cofv_ld2(scr, BLSW_PREPV_ZI(k)), zn = cofv_ld2(scr, BLSW_PREPV_ZI(k + 1));
+    if (zi.c1.l[11] == BLSW_PREPV_DEGENERATE) {  // phase 1 has written this point's witnesses and left the step's coefficients in ST(k)
+        out.st(4 * k + 0, X.c0);
+        out.st(4 * k + 1, X.c1);
+        out.st(4 * k + 2, Y.c0);
+        out.st(4 * k + 3, Y.c1);
+        return;
+    }
     const Fp2 zi2 = v_sqr(zi);
     Fp2 rx = fp2_mul_inl(X, zi2), ry = fp2_mul_inl(Y, fp2_mul_inl(zi2, zi));
     const Fp2 z2 = v_sqr(Z);

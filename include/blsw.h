@@ -252,6 +252,10 @@ int blsw_engine_submit_io(blsw_engine_t* e, const uint64_t* d_pk_xy, const uint6
  *   d_msg     [n][msg_len] bytes                                                        (UInt8::new_witness_vec, constraints.rs:341)
  *   d_witness [n][witness_stride] field elements (48 B each), witness_stride >= layout.n_witness; may be NULL (results only)
  *   d_result  [n] int32, may be NULL
+ * The points are taken as decoded: every curve point is defined input, inside the prime-order subgroup or not (no entry point of the witness
+ * path makes a subgroup check, and the circuit's allocations accept such points too); the vector is the circuit's on that point in every engine
+ * shape (tests/test_chain_edges_gpu.py). A pair (x, y) that is not on the curve is out of scope: the reference's deserialisation rejects it, so
+ * nothing defines its vector.
  * Device work is issued when max_steps batches are pending or at blsw_engine_flush; `stream` (hipStream_t, may be NULL)
  * is the stream on which THIS batch's inputs become valid (recorded per submit). Buffers must stay alive until the
  * step has completed. Steps are numbered 0, 1, 2, ... in submission order (blsw_engine_submitted).
