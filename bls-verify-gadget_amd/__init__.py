@@ -112,6 +112,12 @@ def lib():
         L.blsw_matrices_fill_aggregate_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
         L.blsw_engine_submit_aggregate_io.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
         L.blsw_layout_multi.argtypes = [u32, u32, ctypes.POINTER(blsw_layout_t)]
+        L.blsw_layout_multi_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_layout_t)]
+        L.blsw_matrices_info_multi_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t)]
+        L.blsw_matrices_fill_multi_inputs.argtypes = [u32, u32, u32, ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)]
+        L.blsw_engine_submit_multi_io.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]
+        L.blsw_engine_workspace_bytes_multi_inputs.argtypes = [u64, u32, u32, u32, ctypes.POINTER(blsw_engine_options_t), u32, ctypes.POINTER(u64)]
+        L.blsw_engine_create_multi_inputs.argtypes = [ctypes.POINTER(vp), u64, u32, u32, u32, ctypes.POINTER(blsw_engine_options_t), u32, vp, u64]
         L.blsw_verify_multi_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
         L.blsw_verify_multi_batch.argtypes = [vp, vp, u32, u32, vp, u64, vp, u64, vp, vp, u64, vp]
         L.blsw_engine_destroy.argtypes = [vp]
@@ -178,7 +184,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_r1cs_check_compact", "blsw_r1cs_evaluate_compact", "blsw_keyset_bytes", "blsw_keyset_create", "blsw_keyset_table", "blsw_keyset_destroy",
                     "blsw_keyset_broadcast_rate", "blsw_engine_submit_aggregate_keyset", "blsw_engine_submit_aggregate_keyset_compact",
                     "blsw_engine_expand_compact_keyset", "blsw_compact_layout_keyset", "blsw_r1cs_head_rows", "blsw_r1cs_handle_head_rows", "blsw_r1cs_check_keyset",
-                    "blsw_r1cs_check_compact_keyset", "blsw_r1cs_evaluate_compact_keyset"]
+                    "blsw_r1cs_check_compact_keyset", "blsw_r1cs_evaluate_compact_keyset", "blsw_layout_multi_inputs", "blsw_matrices_info_multi_inputs",
+                    "blsw_matrices_fill_multi_inputs", "blsw_engine_submit_multi_io", "blsw_engine_workspace_bytes_multi_inputs", "blsw_engine_create_multi_inputs"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -186,6 +193,7 @@ IO_MODES = {"witness": 0, "input": 1, "Witness": 0, "Input": 1}
 
 
 AGG_KEYS_INPUT, AGG_BITMAP_INPUT, AGG_MSG_INPUT, AGG_SIG_INPUT = 1, 2, 4, 8  # include/blsw.h: BLSW_AGG_*_INPUT, the bits of agg_inputs
+MULTI_KEYS_INPUT, MULTI_MSG_INPUT, MULTI_SIG_INPUT = 1, 4, 8  # include/blsw.h: BLSW_MULTI_*_INPUT, the bits of multi_inputs
 
 
 def layout(msg_len=32, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0):
@@ -252,7 +260,7 @@ def check_capacity(device, what, *byte_counts):
 
 def engine_options(**overrides):
     """blsw_engine_options_default with keyword overrides: device, pairing_mode ("team"/"lane" or 0/1), g2_mode ("lane"/"team"
-    or 0/1), expand_variant, expand_store, prio_mode, place_lds, consumer_mode, output_form, n_keys, agg_inputs (mask of AGG_*_INPUT). The library itself reads no
+    or 0/1), expand_variant, expand_store, prio_mode, place_lds, consumer_mode, output_form, n_keys, agg_inputs (mask of AGG_*_INPUT), n_pairs. The library itself reads no
     environment for its options (one diagnostic: BLSW_TRACE_GROUP=1 prints every launch group's stage times at engine destruction); for A/B runs of measurement scripts THIS function applies BLSW_PAIRING=lane, BLSW_G2=team, BLSW_EXPAND_VARIANT,
     BLSW_EXPAND_NT, BLSW_PRIO_MODE, BLSW_PLACE_LDS (explicit keyword arguments win)."""
     o = blsw_engine_options_t()
@@ -386,7 +394,8 @@ class WitnessEngine:
     Streaming consumers use the step numbers returned by submit(): wait_step(seq) / output_consumed(tensor)."""
 
     def __init__(self, n, msg_len=32, max_steps=1, device=None, n_buffers=None, reserve_bytes=0, **options):
-        """options: fields of blsw_engine_options_t; n_keys=K makes it an aggregate_verify engine (submit_aggregate).
+        """options: fields of blsw_engine_options_t; n_keys=K makes it an aggregate_verify engine (submit_aggregate). multi_inputs=mask (with n_pairs=K,
+        MULTI_*_INPUT): the N+1-pair product with Input arguments — no field of the struct, the argument of blsw_engine_create_multi_inputs.
         reserve_bytes: bytes the caller will allocate next to the workspace (its witness tensors): the capacity check, made with the byte count
         blsw_engine_workspace_bytes_ex returns for THESE options and this n_buffers, covers them too (BlswError instead of an allocator exception)."""
         torch = _require_cuda()
@@ -394,6 +403,7 @@ class WitnessEngine:
         self.n, self.msg_len, self.max_steps = int(n), int(msg_len), int(max_steps)
         self.n_buffers = int(n_buffers) if n_buffers is not None else (3 if self.max_steps > 1 else 1)
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.multi_inputs = int(options.pop("multi_inputs", 0) or 0)
         opt = engine_options(**options)
         opt.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self._opt = opt
@@ -402,19 +412,19 @@ class WitnessEngine:
         self.msg_mode = int(opt.msg_mode)
         self.agg_inputs = int(opt.agg_inputs)
         self.shared_keys = int(opt.shared_keys)
-        self.layout = layout_aggregate(msg_len, self.n_keys, self.agg_inputs) if self.n_keys else (layout_multi(msg_len, self.n_pairs) if self.n_pairs > 1 else
+        self.layout = layout_aggregate(msg_len, self.n_keys, self.agg_inputs) if self.n_keys else (layout_multi(msg_len, self.n_pairs, self.multi_inputs) if self.n_pairs > 1 else
                                                                                   layout(msg_len, int(opt.params_mode), int(opt.pk_mode), int(opt.sig_mode), self.msg_mode))
         self.n_witness = self.layout["n_witness"]
         self.n_instance_vars = self.layout["n_instance_vars"]
         wb = ctypes.c_uint64(0)
-        rc = lib().blsw_engine_workspace_bytes_ex(self.n, self.msg_len, self.max_steps, self.n_buffers, ctypes.byref(opt), ctypes.byref(wb))
+        rc = lib().blsw_engine_workspace_bytes_multi_inputs(self.n, self.msg_len, self.max_steps, self.n_buffers, ctypes.byref(opt), self.multi_inputs, ctypes.byref(wb))
         if rc:
             raise BlswError("blsw_engine_workspace_bytes_ex failed: %d" % rc)
         check_capacity(self.device, "WitnessEngine (n = %d, max_steps = %d, n_buffers = %d)" % (self.n, self.max_steps, self.n_buffers), wb.value, reserve_bytes)
         self.workspace = torch.empty(wb.value, dtype=torch.uint8, device=self.device)
         self._e = ctypes.c_void_p()
-        rc = lib().blsw_engine_create_ex(ctypes.byref(self._e), self.n, self.msg_len, self.max_steps, self.n_buffers, ctypes.byref(opt), self.workspace.data_ptr(),
-                                         self.workspace.numel())
+        rc = lib().blsw_engine_create_multi_inputs(ctypes.byref(self._e), self.n, self.msg_len, self.max_steps, self.n_buffers, ctypes.byref(opt), self.multi_inputs,
+                                                   self.workspace.data_ptr(), self.workspace.numel())
         if rc:
             self._e = None
             raise BlswError("blsw_engine_create_ex failed: %d" % rc)
@@ -488,20 +498,26 @@ class WitnessEngine:
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq, pk_xy, sig_xy, status
 
-    def submit_multi(self, pks_xy, msgs, sig_xy, witness=None, result=None, stream=None):
-        """N+1-pair product batch (engine created with n_pairs=K): pks_xy [n, K, 12] int64, msgs [n, K, msg_len] uint8, sig_xy [n, 24] -> step number"""
+    def submit_multi(self, pks_xy, msgs, sig_xy, witness=None, result=None, stream=None, instance=None):
+        """N+1-pair product batch (engine created with n_pairs=K): pks_xy [n, K, 12] int64, msgs [n, K, msg_len] uint8, sig_xy [n, 24] -> step number.
+        instance: [n, n_instance_vars, 6] tensor that receives instance_assignment (blsw_engine_submit_multi_io; multi_inputs engines: the message
+        chunks, keys and signature an arkworks verifier takes as public inputs, in that order)."""
         K = self.n_pairs
         assert K > 1 and pks_xy.shape == (self.n, K, 12) and msgs.shape == (self.n, K, self.msg_len) and sig_xy.shape == (self.n, 24)
         assert pks_xy.is_contiguous() and msgs.is_contiguous() and sig_xy.is_contiguous()
         if witness is not None:
             assert witness.is_contiguous() and witness.shape[0] == self.n and witness.shape[1] >= self.n_witness
         seq = self.submitted()
-        rc = lib().blsw_engine_submit_multi(self._e, pks_xy.data_ptr(), msgs.data_ptr() if self.msg_len else None, sig_xy.data_ptr(),
-                                            witness.data_ptr() if witness is not None else None, witness.shape[1] if witness is not None else 0,
-                                            result.data_ptr() if result is not None else None, self._stream(stream))
+        tail = (witness.data_ptr() if witness is not None else None, witness.shape[1] if witness is not None else 0,
+                result.data_ptr() if result is not None else None, self._stream(stream))
+        if instance is not None:
+            assert instance.is_contiguous() and tuple(instance.shape) == (self.n, self.n_instance_vars, 6)
+            rc = lib().blsw_engine_submit_multi_io(self._e, pks_xy.data_ptr(), msgs.data_ptr() if self.msg_len else None, sig_xy.data_ptr(), instance.data_ptr(), *tail)
+        else:
+            rc = lib().blsw_engine_submit_multi(self._e, pks_xy.data_ptr(), msgs.data_ptr() if self.msg_len else None, sig_xy.data_ptr(), *tail)
         if rc:
             raise (BlswBusy if rc == ERR_BUSY else BlswError)("blsw_engine_submit_multi failed: %d" % rc)
-        self._keep.append((pks_xy, msgs, sig_xy, witness, result))
+        self._keep.append((pks_xy, msgs, sig_xy, witness, result, instance))
         self._keep = self._keep[-(self.n_buffers + 1) * self.max_steps:]
         return seq
 
@@ -1116,12 +1132,13 @@ def aggregate_verify(parameters, public_keys, bitmap, message, signature, want_w
     return res, cnt, wit
 
 
-def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0, agg_inputs=0):
+def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, msg_mode=0, agg_inputs=0, multi_inputs=0):
     """Constraint matrices of a circuit shape (host only; blsw_matrices_info + blsw_matrices_fill): the R1CS an arkworks prover
     takes next to the witness vectors, in ConstraintMatrices shape. Returns dict(n_constraints, n_instance_vars, n_witness,
     A / B / C = (row_ptr uint64 [n_constraints + 1], col uint32 [nnz], val uint64 [nnz, 6] Montgomery limbs)).
     params_mode 1 / "witness" (single-key circuit): the system of layout(msg_len, params_mode=1); msg_mode / pk_mode / sig_mode as layout();
-    agg_inputs (with n_keys): the system of layout_aggregate(msg_len, n_keys, agg_inputs)."""
+    agg_inputs (with n_keys): the system of layout_aggregate(msg_len, n_keys, agg_inputs); multi_inputs (the N+1-pair product): the system of
+    layout_multi(msg_len, n_pairs, multi_inputs)."""
     import numpy as np
 
     params_mode = PARAMS_MODES.get(params_mode, params_mode)
@@ -1130,7 +1147,12 @@ def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode
     if agg_inputs and (not n_keys or n_pairs != 1 or params_mode):
         raise BlswError("agg_inputs applies to the aggregate_verify circuit (n_keys > 0)")
     agg = bool(agg_inputs) and not (msg_mode or pk_mode or sig_mode)  # the three single-key modes stay refused together with n_keys, below
-    if agg:
+    if multi_inputs and (n_keys or params_mode or agg_inputs):
+        raise BlswError("multi_inputs applies to the N+1-pair product (n_keys 0, Constant parameters)")
+    multi = bool(multi_inputs) and not (msg_mode or pk_mode or sig_mode)  # and together with n_pairs != 1
+    if multi:
+        rc = lib().blsw_matrices_info_multi_inputs(msg_len, n_pairs, multi_inputs, ctypes.byref(info))
+    elif agg:
         rc = lib().blsw_matrices_info_aggregate_inputs(msg_len, n_keys, agg_inputs, ctypes.byref(info))
     elif msg_mode:  # columns: 0 = one, the message chunks, the key's and the signature's inputs, then the witnesses
         if n_keys or n_pairs != 1 or params_mode:
@@ -1157,7 +1179,9 @@ def matrices(msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode
         out.row_ptr[m] = rp[m].ctypes.data_as(u64p)
         out.col[m] = col[m].ctypes.data_as(u32p)
         out.val[m] = val[m].ctypes.data_as(u64p)
-    if agg:
+    if multi:
+        rc = lib().blsw_matrices_fill_multi_inputs(msg_len, n_pairs, multi_inputs, ctypes.byref(info), ctypes.byref(out))
+    elif agg:
         rc = lib().blsw_matrices_fill_aggregate_inputs(msg_len, n_keys, agg_inputs, ctypes.byref(info), ctypes.byref(out))
     elif msg_mode:
         rc = lib().blsw_matrices_fill_inputs(msg_len, msg_mode, pk_mode, sig_mode, ctypes.byref(info), ctypes.byref(out))
@@ -1217,10 +1241,10 @@ class ConstraintChecker:
     public inputs), form 0 = Montgomery, 1 = canonical (options.output_form). The encoded matrices live in a device tensor this object
     owns; it is read-only after construction and recorded on every stream a call runs on."""
 
-    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None, msg_mode=0, agg_inputs=0):
+    def __init__(self, msg_len=32, n_keys=0, n_pairs=1, params_mode=0, pk_mode=0, sig_mode=0, device=None, _mats=None, msg_mode=0, agg_inputs=0, multi_inputs=0):
         torch = _require_cuda()
         self.torch = torch
-        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode, msg_mode, agg_inputs)
+        mats = _mats if _mats is not None else matrices(msg_len, n_keys, n_pairs, params_mode, pk_mode, sig_mode, msg_mode, agg_inputs, multi_inputs)
         self.n_constraints, self.n_instance_vars, self.n_witness = int(mats["n_constraints"]), int(mats["n_instance_vars"]), int(mats["n_witness"])
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         if self.device.index is None:
@@ -1412,9 +1436,13 @@ class ConstraintChecker:
         return tuple(out)
 
 
-def layout_multi(msg_len, n_pairs):
+def layout_multi(msg_len, n_pairs, multi_inputs=0):
+    """Segment table of the N+1-pair product; multi_inputs: mask of MULTI_*_INPUT (blsw_layout_multi_inputs), 0 = every argument Witness"""
     L = blsw_layout_t()
-    rc = lib().blsw_layout_multi(msg_len, n_pairs, ctypes.byref(L))
+    if multi_inputs:
+        rc = lib().blsw_layout_multi_inputs(msg_len, n_pairs, multi_inputs, ctypes.byref(L))
+    else:
+        rc = lib().blsw_layout_multi(msg_len, n_pairs, ctypes.byref(L))
     if rc:
         raise BlswError("blsw_layout_multi failed: %d" % rc)
     return {n: getattr(L, n) for n in _LAYOUT_FIELDS}
@@ -1423,13 +1451,38 @@ def layout_multi(msg_len, n_pairs):
 def verify_multi(parameters, public_keys, messages, signature, want_witness=True):
     """N+1-pair product of pairings: one signature over K (pk_j, msg_j) pairs per instance, i.e. constraints.rs:90-128 with
     product_of_pairings over slices of K + 1 prepared points. public_keys.xy [n, K, 12] int64, messages [n, K, msg_len] uint8,
-    signature.xy [n, 24]. Returns (result int32 [n], witness [n, n_witness, 6] int64 or None)."""
+    signature.xy [n, 24]. Returns (result int32 [n], witness [n, n_witness, 6] int64 or None).
+    messages may be a UInt8 vector. With an argument allocated as Input (PublicKeyVar.new_input, UInt8.new_input_vec, SignatureVar.new_input; K >= 2)
+    the circuit is the one of layout_multi(msg_len, K, mask): a one-step engine runs it and the call returns (result, witness, instance) with
+    instance [n, n_instance_vars, 6] = every instance's instance_assignment."""
     torch = _require_cuda()
     assert isinstance(parameters, ParametersVar)
-    pks, sig, messages = public_keys.xy.contiguous(), signature.xy.contiguous(), messages.contiguous()
+    msg_var = messages if isinstance(messages, UInt8) else UInt8(messages)
+    mask = ((MULTI_KEYS_INPUT if public_keys.mode == "Input" else 0) | (MULTI_MSG_INPUT if msg_var.mode == "Input" else 0) |
+            (MULTI_SIG_INPUT if signature.mode == "Input" else 0))
+    pks, sig, messages = public_keys.xy.contiguous(), signature.xy.contiguous(), msg_var.bytes.contiguous()
     n, K = pks.shape[0], pks.shape[1]
     assert K >= 1 and messages.shape[:2] == (n, K) and sig.shape == (n, 24) and pks.shape == (n, K, 12)
     msg_len = messages.shape[2]
+    if mask:
+        if parameters.mode != "Constant":
+            raise BlswError("verify_multi with Input arguments: ParametersVar allocated as %s is not offered (Constant)" % parameters.mode)
+        if K < 2:
+            raise BlswError("verify_multi with Input arguments needs at least two pairs (one pair: BlsSignatureVerifyGadget with pk_mode / sig_mode / msg_mode)")
+        lay = layout_multi(msg_len, K, mask)
+        # an N+1-pair engine is a staged one: one step per group, two group buffers
+        eng = WitnessEngine(n, msg_len, max_steps=1, n_buffers=2, device=pks.device, reserve_bytes=n * lay["n_witness"] * 48 if want_witness else 0, n_pairs=K,
+                            multi_inputs=mask)
+        try:
+            res = torch.empty(n, dtype=torch.int32, device=pks.device)
+            wit = eng.new_witness_tensor() if want_witness else None
+            inst = eng.new_instance_tensor()
+            eng.submit_multi(pks, messages, sig, witness=wit, result=res, instance=inst)
+            eng.flush()
+            torch.cuda.synchronize(pks.device)
+        finally:
+            eng.close()
+        return res, wit, inst
     lay = layout_multi(msg_len, K)
     wb = ctypes.c_uint64(0)
     rc = lib().blsw_verify_multi_workspace_bytes(n, msg_len, K, ctypes.byref(wb))

@@ -118,6 +118,7 @@ struct blsw_engine {
     uint32_t head = 0;
     Modes modes = DEFAULT_MODES;
     blsw_engine_options_t opt;
+    uint32_t multi_inputs = 0;  // BLSW_MULTI_*_INPUT of an N+1-pair engine (blsw_engine_create_multi_inputs)
     int device = -1;
     GroupBuf buf[BLSW_MAX_BUFFERS];
     int nbuf = 0;
@@ -394,22 +395,27 @@ static Group make_group(uint64_t steps, uint64_t n, uint32_t K, uint32_t msg_len
 }
 
 // the circuit an engine's options select (checked by check_options): the aggregate circuit takes its allocation modes from agg_inputs, the
-// single-key circuit and the N+1-pair product from params_mode / pk_mode / sig_mode / msg_mode
-static void options_layout(uint32_t msg_len, const blsw_engine_options_t* o, blsw_layout_t* L) {
+// N+1-pair product from the mask multi_inputs of blsw_engine_create_multi_inputs, the single-key circuit from params_mode / pk_mode / sig_mode / msg_mode
+static void options_layout(uint32_t msg_len, const blsw_engine_options_t* o, uint32_t multi_inputs, blsw_layout_t* L) {
     if (o->n_keys)
         make_layout_aggregate(msg_len, L, o->n_keys, o->agg_inputs);
+    else if (o->n_pairs > 1)
+        make_layout_multi(msg_len, L, o->n_pairs, multi_inputs);
     else
         make_layout(msg_len, L, 0, o->n_pairs > 1 ? o->n_pairs : 1, o->params_mode == 1, o->pk_mode == 1, o->sig_mode == 1, o->msg_mode == 1);
 }
 // the layout of the rows such an engine computes itself (blsw_engine::LR): with options.shared_keys the circuit's layout without its keys segment
-static void options_layout_rows(uint32_t msg_len, const blsw_engine_options_t* o, blsw_layout_t* L) {
+static void options_layout_rows(uint32_t msg_len, const blsw_engine_options_t* o, uint32_t multi_inputs, blsw_layout_t* L) {
     if (o->shared_keys)
         make_layout_aggregate(msg_len, L, o->n_keys, o->agg_inputs | BLSW_AGG_KEYS_INPUT);
     else
-        options_layout(msg_len, o, L);
+        options_layout(msg_len, o, multi_inputs, L);
 }
 // is the message allocated with UInt8::new_input_vec?
-static bool options_msg_input(const blsw_engine_options_t* o) { return o->n_keys ? (o->agg_inputs & BLSW_AGG_MSG_INPUT) != 0 : o->msg_mode == 1; }
+static bool options_msg_input(const blsw_engine_options_t* o, uint32_t multi_inputs) {
+    if (o->n_keys) return (o->agg_inputs & BLSW_AGG_MSG_INPUT) != 0;
+    return o->n_pairs > 1 ? (multi_inputs & BLSW_MULTI_MSG_INPUT) != 0 : o->msg_mode == 1;
+}
 
 static int launch_group(blsw_engine* e) {
     GroupBuf& b = e->buf[e->cur];
@@ -419,7 +425,7 @@ static int launch_group(blsw_engine* e) {
     // per-pair view: one lane per (instance, pair)
     Group g = make_group(steps, e->n, K, e->msg_len, b.d_desc, e->L, carve(b.base, (uint64_t)steps * e->n * K, e->LR, e->staged, e->modes, (uint64_t)steps * e->n));
     g.LS = e->LS;
-    const bool msg_input = options_msg_input(&e->opt);
+    const bool msg_input = options_msg_input(&e->opt, e->multi_inputs);
     if (msg_input) g.msg_wit_len = 0;  // UInt8::new_input_vec: k_msg_input writes the message segment, k_sha no message booleans
     g.chain_prio = e->opt.prio_mode == 0;
     g.canonical = (int)e->opt.output_form;
@@ -590,7 +596,7 @@ static void launch_cofactor_direct(const ChainKernels& ck, bool vf, const Group&
 
 // Every rule on an engine's arguments and options that does not need the device: blsw_engine_workspace_bytes_ex and blsw_engine_create_ex
 // refuse the same sets (BLSW_ERR_ARG)
-static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* o) {
+static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* o, uint32_t multi_inputs = 0) {
     // n is the y extent of the expansion / canonical-form launches (one row of workgroups per instance): at most 65535
     if (!o || n == 0 || n > 65535 || max_steps == 0 || n_buffers == 0 || n_buffers > BLSW_MAX_BUFFERS || msg_len > 65535) return BLSW_ERR_ARG;
     const bool staged = max_steps > 1 || n_buffers > 1;
@@ -614,6 +620,8 @@ static int check_options(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint3
     if (o->agg_inputs > 15 || (o->agg_inputs && !o->n_keys)) return BLSW_ERR_ARG;
     // a shared key set per step: an aggregate engine whose keys are allocated as witnesses
     if (o->shared_keys > 1 || (o->shared_keys && (!o->n_keys || (o->agg_inputs & BLSW_AGG_KEYS_INPUT)))) return BLSW_ERR_ARG;
+    // the N+1-pair product's own allocation modes (BLSW_MULTI_*_INPUT): an N+1-pair engine only (the other circuits' modes are refused with it above)
+    if (!multi_inputs_ok(multi_inputs) || (multi_inputs && o->n_pairs < 2)) return BLSW_ERR_ARG;
     return BLSW_OK;
 }
 
@@ -645,6 +653,14 @@ int blsw_layout_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_mode, ui
     return BLSW_OK;
 }
 
+int blsw_layout_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, blsw_layout_t* out) {
+    if (!out || msg_len > 65535 || n_pairs == 0 || n_pairs > 4096 || !multi_inputs_ok(multi_inputs)) return BLSW_ERR_ARG;
+    make_layout_multi(msg_len, out, n_pairs, multi_inputs);
+    const uint64_t total = (uint64_t)out->off_prep_h - out->off_expand;  // as blsw_layout_multi: 32-bit element offsets
+    if (total / n_pairs != out->stride_hash) return BLSW_ERR_ARG;
+    return BLSW_OK;
+}
+
 int blsw_engine_options_default(blsw_engine_options_t* o) {
     if (!o) return BLSW_ERR_ARG;
     o->device = -1;
@@ -672,11 +688,15 @@ int blsw_engine_options_default(blsw_engine_options_t* o) {
 }
 
 int blsw_engine_workspace_bytes_ex(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options, uint64_t* bytes) {
+    return blsw_engine_workspace_bytes_multi_inputs(n, msg_len, max_steps, n_buffers, options, 0, bytes);
+}
+int blsw_engine_workspace_bytes_multi_inputs(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
+                                             uint32_t multi_inputs, uint64_t* bytes) {
     if (!bytes) return BLSW_ERR_ARG;
-    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
+    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options, multi_inputs)) return rc;
     blsw_layout_t L;
     const uint32_t K = options->n_pairs > 1 ? options->n_pairs : 1;
-    options_layout_rows(msg_len, options, &L);
+    options_layout_rows(msg_len, options, multi_inputs, &L);
     const bool staged = max_steps > 1 || n_buffers > 1;
     // the same workspace serves every kernel variant: the largest carve of the three mode combinations
     uint64_t need = 0;
@@ -704,8 +724,12 @@ int blsw_engine_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t max_steps
 
 int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
                           void* d_workspace, uint64_t workspace_bytes) {
+    return blsw_engine_create_multi_inputs(out, n, msg_len, max_steps, n_buffers, options, 0, d_workspace, workspace_bytes);
+}
+int blsw_engine_create_multi_inputs(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
+                                    uint32_t multi_inputs, void* d_workspace, uint64_t workspace_bytes) {
     if (!out || !d_workspace) return BLSW_ERR_ARG;
-    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options)) return rc;
+    if (int rc = check_options(n, msg_len, max_steps, n_buffers, options, multi_inputs)) return rc;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BLSW_ERR_NO_DEVICE;
@@ -714,7 +738,7 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     if (dev >= ndev) return BLSW_ERR_ARG;
     DeviceGuard guard(dev);
     uint64_t need = 0;
-    blsw_engine_workspace_bytes_ex(n, msg_len, max_steps, n_buffers, options, &need);  // cannot fail: the options have been checked
+    blsw_engine_workspace_bytes_multi_inputs(n, msg_len, max_steps, n_buffers, options, multi_inputs, &need);  // cannot fail: the options have been checked
     if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
     // Scratch guard. ROCr backs a queue's scratch for full-device occupancy: stack bytes per lane x 64 lanes x wave slots
     // (CUs x 32), per queue that runs the kernel. The single-lane pairing kernel (9.7 KB of stack) on four or more group
@@ -737,14 +761,15 @@ int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uin
     e->msg_len = msg_len;
     e->max_steps = max_steps;
     e->opt = *options;
+    e->multi_inputs = multi_inputs;
     e->opt.device = dev;
     e->device = dev;
     e->modes = {options->pairing_mode == 0, options->g2_mode == 1};
     e->staged = max_steps > 1 || n_buffers > 1;
     e->cofactor_mode = options->cofactor_mode;
     e->chains_inlined = options->chain_variant == 2 || (options->chain_variant == 0 && !e->staged);
-    options_layout(msg_len, options, &e->L);
-    options_layout_rows(msg_len, options, &e->LR);
+    options_layout(msg_len, options, multi_inputs, &e->L);
+    options_layout_rows(msg_len, options, multi_inputs, &e->LR);
     e->head = options->shared_keys ? options->n_keys * SEG_PK_ALLOC : 0;
     e->LS = e->L.n_pairs > 1 ? staging_layout_multi(e->L).LS : staging_layout(e->LR, e->modes);
     for (int i = 0; i < BLSW_MAX_CONSUMED; i++) {
@@ -899,6 +924,13 @@ int blsw_engine_submit_multi(blsw_engine_t* e, const uint64_t* d_pks_xy, const u
     StepDesc d = {d_pks_xy, d_sig_xy, d_msgs, d_witness, witness_stride, d_result, nullptr, nullptr, nullptr, nullptr, nullptr};
     return engine_submit(e, d, stream_);
 }
+// the same step with its instance_assignment (every N+1-pair engine; the mask it was created with says which arguments are public inputs)
+int blsw_engine_submit_multi_io(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_msgs, const uint64_t* d_sig_xy, uint64_t* d_instance, uint64_t* d_witness,
+                                uint64_t witness_stride, int32_t* d_result, void* stream_) {
+    if (!e || e->L.n_pairs < 2 || !d_pks_xy || !d_sig_xy || (!d_msgs && e->msg_len)) return BLSW_ERR_ARG;
+    StepDesc d = {d_pks_xy, d_sig_xy, d_msgs, d_witness, witness_stride, d_result, nullptr, nullptr, nullptr, nullptr, nullptr, d_instance};
+    return engine_submit(e, d, stream_);
+}
 // One call from compressed bytes: decode on `stream`, then the step; result[i] = gadget Boolean AND both points decoded
 // to non-identity subgroup points (tests/tests.rs:244-263: a point that fails to decode is replaced by the default — the identity —
 // and the case must come out false). The decoded coordinates live in caller buffers (they are the step's inputs).
@@ -954,7 +986,7 @@ int blsw_compact_layout(uint64_t n, uint32_t msg_len, const blsw_engine_options_
     if (!out || !options || n % 64 || options->n_pairs > 1 || options->shared_keys) return BLSW_ERR_ARG;
     if (int rc = check_options(n, msg_len, 2, 1, options)) return rc;  // any staged engine: the step's form does not depend on max_steps / n_buffers
     blsw_layout_t L;
-    options_layout(msg_len, options, &L);
+    options_layout(msg_len, options, 0, &L);
     *out = compact_layout(n, L, Modes{options->pairing_mode == 0, options->g2_mode == 1});
     return BLSW_OK;
 }
@@ -964,7 +996,7 @@ int blsw_compact_layout_keyset(uint64_t n, uint32_t msg_len, const blsw_engine_o
     if (!rows || !head_len || !options || n % 64 || options->n_pairs > 1 || !options->shared_keys) return BLSW_ERR_ARG;
     if (int rc = check_options(n, msg_len, 2, 1, options)) return rc;
     blsw_layout_t L;
-    options_layout_rows(msg_len, options, &L);
+    options_layout_rows(msg_len, options, 0, &L);
     *rows = compact_layout(n, L, Modes{options->pairing_mode == 0, options->g2_mode == 1});
     *head_len = options->n_keys * SEG_PK_ALLOC;
     return BLSW_OK;

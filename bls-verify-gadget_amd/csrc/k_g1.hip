@@ -2,6 +2,7 @@
 // A chain unit: its compilations and the register policy of its grouped compilation are its entry in build.py's CHAIN_UNITS.
 #include "kcommon.hpp"
 #include "agg_input.hpp"
+#include "multi_input.hpp"
 
 namespace blsw {
 
@@ -29,17 +30,13 @@ __global__ __launch_bounds__(64) BLSW_CHAIN_ATTR void BLSW_K(k_g1)(Group g) {
     Proj<OpsFp> pk;
     if (g.L.pk_mode && !params) {
         // PublicKeyVar::new_variable(Input) (constraints.rs:214-232) = new_variable_omit_prime_order_check: x, y, z are public inputs (after the
-        // message's, before the signature's: 1 + c .. 3 + c of instance_assignment for c message inputs), no witnesses, no in-circuit prime-order check
-        const bool inf = fp_is_zero(x) && fp_is_zero(y);
-        pk = {inf ? fp_zero() : x, inf ? fp_one() : y, inf ? fp_zero() : fp_one()};
-        const uint32_t k0 = g.L.n_instance_vars - 3 - (g.L.sig_mode ? 6 : 0);
-        put_instance(g, id, k0, pk.x);
-        put_instance(g, id, k0 + 1, pk.y);
-        put_instance(g, id, k0 + 2, pk.z);
+        // messages', before the signature's; pair j's own three in the N+1-pair product: multi_input.hpp), no witnesses, no in-circuit prime-order
+        // check: a pair lane then runs only chain_g1_post
+        pk = multi_key_input(g.L, id.j, x, y, [&](uint32_t k, const Fp& v) { put_instance(g, id, k, v); });
     } else {
         pk = chain_g1_alloc_only(e_alloc, x, y);
     }
-    if (!params) put_instance(g, id, 0, fp_one());  // instance_assignment[0]
+    if (!params && id.j == 0) put_instance(g, id, 0, fp_one());  // instance_assignment[0], once per instance
     if (params) pk.y = fp_neg(pk.y);
     G1ChainOut o = chain_g1_post(e_nz, e_prep, pk);
     if (params) return;  // its affine form is the constant the pairing kernel uses

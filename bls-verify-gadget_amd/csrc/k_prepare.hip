@@ -1,6 +1,7 @@
 // libblsw.so, one translation unit per kernel family (see kcommon.hpp, build.py).
 // A chain unit: its compilations and the register policy of its grouped compilation are its entry in build.py's CHAIN_UNITS.
 #include "kcommon.hpp"
+#include "multi_input.hpp"
 
 namespace blsw {
 
@@ -23,7 +24,7 @@ __device__ __forceinline__ Proj<OpsFp2> prepare_point(const Group& g, const Lane
 // of instance_assignment; the prepare chain of the signature is the kernel that has the point at hand (there is no allocation chain in this mode)
 __device__ __forceinline__ void put_sig_instance(const Group& g, const LaneId& id, const Proj<OpsFp2>& q) {
     if (!g.L.sig_mode || !item_leader()) return;
-    const uint32_t k0 = g.L.n_instance_vars - 6;
+    const uint32_t k0 = multi_inst_sig(g.L, 0);
     put_instance(g, id, k0 + 0, q.x.c0);
     put_instance(g, id, k0 + 1, q.x.c1);
     put_instance(g, id, k0 + 2, q.y.c0);

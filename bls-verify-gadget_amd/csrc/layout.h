@@ -39,6 +39,8 @@ inline uint32_t seg_miller(uint32_t n_pairs) { return 62 * 36 + 68 * 30 - 30 + 6
 // msg_input: UInt8::new_input_vec (ark-r1cs-std 0.4.0), single-key circuit with Constant parameters only: the message is packed into
 // msg_input_chunks(msg_len) public inputs of MSG_CHUNK_BYTES bytes each, allocated before the key's and the signature's, and the message segment
 // holds each chunk's AllocatedFp::to_bits_le (SEG_MSG_CHUNK witnesses per chunk) instead of 8 booleans per byte.
+// The N+1-pair product (n_pairs > 1) takes the same three flags for its K keys, its K messages and its signature (blsw_layout_multi_inputs): each
+// Input argument is the single-key rule K times, the instance variables in allocation order msgs, pks, sig (multi_input.hpp).
 // aggregate_verify (n_keys > 0) takes the same three flags for its keys (every key Input: 3 n_keys instance variables, an empty keys segment), its
 // message and its signature, and bitmap_input for Boolean::new_input per bit (n_keys instance variables, an empty bitmap segment; the booleanity
 // constraints stay). Allocation order keys, bitmap, message, signature (constraints.rs:394-441) is the order of the instance variables.
@@ -51,7 +53,8 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
     expand_message_w(s, msg.data(), msg_len, false, uw);
     L->msg_len = msg_len;
     const uint32_t msg_chunks = msg_input ? msg_input_chunks(msg_len) : 0;
-    L->n_instance_vars = 1 + msg_chunks + (pk_input ? 3 * (n_keys ? n_keys : 1) : 0) + (n_keys && bitmap_input ? n_keys : 0) + (sig_input ? 6 : 0);
+    const uint32_t K = n_keys ? 1 : (n_pairs ? n_pairs : 1);
+    L->n_instance_vars = 1 + msg_chunks * K + (pk_input ? 3 * (n_keys ? n_keys : K) : 0) + (n_keys && bitmap_input ? n_keys : 0) + (sig_input ? 6 : 0);
     L->pk_mode = pk_input ? 1 : 0;
     L->sig_mode = sig_input ? 1 : 0;
     L->sha_bits = (uint32_t)s.nbits;
@@ -64,7 +67,6 @@ inline void make_layout(uint32_t msg_len, blsw_layout_t* L, uint32_t n_keys = 0,
         L->off_bitmap = o;
         o += bitmap_input ? 0 : n_keys;
     }
-    const uint32_t K = n_keys ? 1 : (n_pairs ? n_pairs : 1);
     L->n_pairs = K;
     L->stride_msg = msg_input ? SEG_MSG_CHUNK * msg_chunks : 8 * msg_len;
     L->stride_pk_alloc = pk_input ? 0 : SEG_PK_ALLOC;
@@ -122,6 +124,11 @@ inline void make_layout_aggregate(uint32_t msg_len, blsw_layout_t* L, uint32_t n
     make_layout(msg_len, L, n_keys, 1, false, (agg_inputs & BLSW_AGG_KEYS_INPUT) != 0, (agg_inputs & BLSW_AGG_SIG_INPUT) != 0, (agg_inputs & BLSW_AGG_MSG_INPUT) != 0,
                 (agg_inputs & BLSW_AGG_BITMAP_INPUT) != 0);
 }
+// the N+1-pair product with its mask of Input arguments (BLSW_MULTI_*_INPUT, include/blsw.h)
+inline void make_layout_multi(uint32_t msg_len, blsw_layout_t* L, uint32_t n_pairs, uint32_t multi_inputs) {
+    make_layout(msg_len, L, 0, n_pairs, false, (multi_inputs & BLSW_MULTI_KEYS_INPUT) != 0, (multi_inputs & BLSW_MULTI_SIG_INPUT) != 0, (multi_inputs & BLSW_MULTI_MSG_INPUT) != 0);
+}
+inline bool multi_inputs_ok(uint32_t multi_inputs) { return multi_inputs <= 15 && !(multi_inputs & 2); }
 // the instance variables of an aggregate_verify layout: [1 | 3 per key | 1 per bitmap bit | message chunks | 6 of the signature], the selected groups only
 BLSW_HD uint32_t agg_bitmap_is_input(const blsw_layout_t& L) { return L.n_keys && L.off_msg == L.off_bitmap; }
 BLSW_HD uint32_t agg_inst_bitmap_base(const blsw_layout_t& L) { return 1 + (L.pk_mode ? 3 * L.n_keys : 0); }

@@ -1289,16 +1289,22 @@ static void circuit(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, bool pa
 
 // io_modes: bit 0 = pk Input, bit 1 = sig Input, bit 2 = msg Input (single-key circuit with Constant parameters); bit 3 = bitmap Input: the
 // aggregate circuit, whose keys, signature and message take bits 0-2 (the callers translate BLSW_AGG_*_INPUT; io_modes >= 16 marks an aggregate
-// circuit reached through blsw_matrices_*_aggregate_inputs: n_keys with io_modes through the other entry points stays refused)
-enum : uint32_t { IO_PK = 1, IO_SIG = 2, IO_MSG = 4, IO_BITMAP = 8, IO_AGG = 16 };
+// circuit reached through blsw_matrices_*_aggregate_inputs: n_keys with io_modes through the other entry points stays refused). IO_MULTI marks the
+// N+1-pair product reached through blsw_matrices_*_multi_inputs, whose K keys, K messages and signature take bits 0-2: n_pairs > 1 with io_modes
+// through the other entry points stays refused too
+enum : uint32_t { IO_PK = 1, IO_SIG = 2, IO_MSG = 4, IO_BITMAP = 8, IO_AGG = 16, IO_MULTI = 32 };
 static int run(uint32_t msg_len, uint32_t n_keys, uint32_t n_pairs, Sys& sys, uint32_t params_mode = 0, uint32_t io_modes = 0) {
     if (msg_len > 65535 || n_keys > 65535 || (n_keys && n_pairs > 1) || n_pairs == 0 || n_pairs > 4096) return BLSW_ERR_ARG;
     if (params_mode > 1 || (params_mode && (n_keys || n_pairs != 1))) return BLSW_ERR_ARG;
-    const bool agg = (io_modes & IO_AGG) != 0;
-    if (io_modes > 31 || (agg && !n_keys) || (!agg && (io_modes > 7 || (io_modes && (n_keys || n_pairs != 1 || params_mode))))) return BLSW_ERR_ARG;
+    const bool agg = (io_modes & IO_AGG) != 0, multi = (io_modes & IO_MULTI) != 0;
+    if (multi) {
+        if ((io_modes & ~(IO_MULTI | IO_PK | IO_SIG | IO_MSG)) || n_keys || params_mode) return BLSW_ERR_ARG;
+    } else if (io_modes > 31 || (agg && !n_keys) || (!agg && (io_modes > 7 || (io_modes && (n_keys || n_pairs != 1 || params_mode)))))
+        return BLSW_ERR_ARG;
     S = &sys;
-    sys.n_inst = 1 + ((io_modes & IO_MSG) ? msg_input_chunks(msg_len) : 0) + ((io_modes & IO_PK) ? 3 * (n_keys ? n_keys : 1) : 0) + ((io_modes & IO_SIG) ? 6 : 0) +
-                 ((io_modes & IO_BITMAP) ? n_keys : 0);
+    // one message and one key per pair (n_pairs == 1 outside the product), n_keys keys in the aggregate circuit
+    sys.n_inst = 1 + ((io_modes & IO_MSG) ? msg_input_chunks(msg_len) * n_pairs : 0) + ((io_modes & IO_PK) ? 3 * (n_keys ? n_keys : n_pairs) : 0) +
+                 ((io_modes & IO_SIG) ? 6 : 0) + ((io_modes & IO_BITMAP) ? n_keys : 0);
     circuit(msg_len, n_keys, n_pairs, params_mode == 1, (io_modes & IO_PK) != 0, (io_modes & IO_SIG) != 0, (io_modes & IO_MSG) != 0, (io_modes & IO_BITMAP) != 0);
     sys.finish();
     S = nullptr;
@@ -1421,5 +1427,19 @@ int blsw_matrices_info_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint3
 int blsw_matrices_fill_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
     if (agg_inputs > 15 || n_keys == 0) return BLSW_ERR_ARG;
     return matrices_fill(msg_len, n_keys, 1, 0, info, out, agg_io_modes(agg_inputs));
+}
+// BLSW_MULTI_*_INPUT -> io_modes of run(); mask 0 is the circuit of blsw_matrices_info(msg_len, 0, n_pairs)
+static uint32_t multi_io_modes(uint32_t m) {
+    using namespace blsw::r1cs;
+    if (!m) return 0;
+    return IO_MULTI | ((m & BLSW_MULTI_KEYS_INPUT) ? IO_PK : 0) | ((m & BLSW_MULTI_MSG_INPUT) ? IO_MSG : 0) | ((m & BLSW_MULTI_SIG_INPUT) ? IO_SIG : 0);
+}
+int blsw_matrices_info_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, blsw_matrices_info_t* out) {
+    if (!blsw::multi_inputs_ok(multi_inputs) || n_pairs == 0) return BLSW_ERR_ARG;
+    return matrices_info(msg_len, 0, n_pairs, 0, out, multi_io_modes(multi_inputs));
+}
+int blsw_matrices_fill_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out) {
+    if (!blsw::multi_inputs_ok(multi_inputs) || n_pairs == 0) return BLSW_ERR_ARG;
+    return matrices_fill(msg_len, 0, n_pairs, 0, info, out, multi_io_modes(multi_inputs));
 }
 }

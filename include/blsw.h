@@ -116,6 +116,21 @@ int blsw_aggregate_verify_batch(const uint64_t* d_pks_xy, const uint8_t* d_bitma
  * Direct mode on the device that owns `stream`. The call copies its descriptor to the device and SYNCHRONISES `stream` once
  * before issuing the kernels (asynchronous from there on); side streams are kept per host thread and device. */
 int blsw_layout_multi(uint32_t msg_len, uint32_t n_pairs, blsw_layout_t* out);
+/* The N+1-pair product with its keys, its messages and its signature Witness (0) or Input, independently: multi_inputs is a mask of */
+#define BLSW_MULTI_KEYS_INPUT 1   /* every PublicKeyVar::new_variable(.., Input)            */
+#define BLSW_MULTI_MSG_INPUT  4   /* every UInt8::new_input_vec                             */
+#define BLSW_MULTI_SIG_INPUT  8   /* SignatureVar::new_variable(.., Input)                  */
+/* The values are BLSW_AGG_*_INPUT's; bit 2 (the aggregate circuit's bitmap) means nothing here. Allocation order is the product's own (msgs, params
+ * Constant, pks, sig), hence the order of the instance variables, the selected groups only, c = ceil(msg_len / 47):
+ *   instance_assignment = [1, m_{0,0} .. m_{0,c-1}, .., m_{K-1,0} .. m_{K-1,c-1}, pk_0.x, pk_0.y, pk_0.z, .., pk_{K-1}.z, sig.x.c0 .. sig.z.c1]
+ * Each Input argument is the single-key rule (blsw_layout_inputs), K times: a key is new_variable_omit_prime_order_check — x, y, z instance variables
+ * ((0, 1, 0) for the (0, 0) input), no witnesses, the key segments are empty (stride_pk_alloc 0); chunk t of message j is instance variable
+ * 1 + j c + t and its to_bits_le is 761 witnesses at off_msg + j * stride_msg + 761 t (stride_msg = 761 c); the signature is six instance variables
+ * and an empty allocation segment. n_instance_vars = 1 + (MSG ? K c : 0) + (KEYS ? 3 K : 0) + (SIG ? 6 : 0); n_witness against blsw_layout_multi changes
+ * by -1942 K (KEYS), -12413 (SIG), +(761 c - 8 msg_len) K (MSG). pk_mode / sig_mode of the layout report the modes, the message's shows in stride_msg.
+ * multi_inputs 0 = blsw_layout_multi field for field; n_pairs 1 = blsw_layout_inputs(msg_len, MSG, KEYS, SIG) field for field.
+ * BLSW_ERR_ARG: bit 2 or a value above 15, n_pairs == 0 or > 4096. Host only. */
+int blsw_layout_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, blsw_layout_t* out);
 /* single-key circuit with ParametersVar::new_variable(.., mode) (src/constraints.rs:198-211): params_mode 0 = Constant (blsw_layout),
  * 1 = Witness. AllocationMode::Input would put the generator into instance_assignment, which this engine does not produce:
  * BLSW_ERR_ARG. Host only. */
@@ -238,6 +253,17 @@ int blsw_engine_create(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32
                        uint64_t workspace_bytes);
 int blsw_engine_create_ex(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
                           void* d_workspace, uint64_t workspace_bytes);
+/* An N+1-pair engine whose keys, messages and signature are Witness or Input: blsw_engine_workspace_bytes_ex / blsw_engine_create_ex with the mask
+ * multi_inputs (BLSW_MULTI_*_INPUT, blsw_layout_multi_inputs) beside the options. The mask is an argument and not a field of blsw_engine_options_t: the
+ * struct, and with it every caller compiled against it, stays as it is. multi_inputs 0 = the _ex functions. A non-zero mask requires options->n_pairs >= 2
+ * and none of n_keys, params_mode, pk_mode, sig_mode, msg_mode, agg_inputs, shared_keys (the product's modes are this mask: pk_mode, sig_mode and
+ * msg_mode stay refused together with n_pairs > 1), and everything an n_pairs engine requires: staged, default kernel modes, n * n_pairs <= 65535.
+ * BLSW_ERR_ARG otherwise, for bit 2 of the mask and for a value above 15; both functions refuse the same sets. Batches go through
+ * blsw_engine_submit_multi_io, which also writes instance_assignment. */
+int blsw_engine_workspace_bytes_multi_inputs(uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
+                                             uint32_t multi_inputs, uint64_t* bytes);
+int blsw_engine_create_multi_inputs(blsw_engine_t** out, uint64_t n, uint32_t msg_len, uint32_t max_steps, uint32_t n_buffers, const blsw_engine_options_t* options,
+                                    uint32_t multi_inputs, void* d_workspace, uint64_t workspace_bytes);
 int blsw_engine_destroy(blsw_engine_t* e);
 /* blsw_engine_submit for an engine with msg_mode / pk_mode / sig_mode Input (it works for every single-key engine): additionally writes
  * d_instance [n][n_instance_vars][6] u64 = each instance's instance_assignment (element 0 = one; Montgomery limbs, or canonical integers with
@@ -294,6 +320,13 @@ int blsw_engine_submit_aggregate_io(blsw_engine_t* e, const uint64_t* d_pks_xy, 
  *   d_witness [n][witness_stride] (stride >= blsw_layout_multi().n_witness; may be NULL), d_result [n] int32 */
 int blsw_engine_submit_multi(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_msgs, const uint64_t* d_sig_xy, uint64_t* d_witness,
                              uint64_t witness_stride, int32_t* d_result, void* stream);
+/* blsw_engine_submit_multi for an engine created with blsw_engine_create_multi_inputs (it works for every N+1-pair engine, mask 0 included: then the witness is
+ * blsw_engine_submit_multi's bit for bit and it writes [1]): additionally writes d_instance [n][n_instance_vars][6] u64 = each instance's
+ * instance_assignment (element 0 = one; Montgomery limbs, or canonical integers with options.output_form 1); d_instance may be NULL.
+ * blsw_engine_submit_multi, blsw_engine_submit_multi_compact and blsw_engine_expand_compact work on an engine with a non-zero mask and write no
+ * instance vector (the compact form carries witnesses only). BLSW_ERR_ARG on an engine with n_pairs < 2. */
+int blsw_engine_submit_multi_io(blsw_engine_t* e, const uint64_t* d_pks_xy, const uint8_t* d_msgs, const uint64_t* d_sig_xy, uint64_t* d_instance, uint64_t* d_witness,
+                                uint64_t witness_stride, int32_t* d_result, void* stream);
 /* Issues everything pending and makes `stream` wait for all batches submitted so far (asynchronous for the host). In consumer
  * mode: for all steps written so far (blsw_engine_materialised); the rest follow as their outputs are released. */
 int blsw_engine_flush(blsw_engine_t* e, void* stream);
@@ -444,6 +477,10 @@ int blsw_matrices_fill_inputs(uint32_t msg_len, uint32_t msg_mode, uint32_t pk_m
  * agg_inputs 0 = blsw_matrices_info / _fill (msg_len, n_keys, 1) */
 int blsw_matrices_info_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, blsw_matrices_info_t* out);
 int blsw_matrices_fill_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out);
+/* The N+1-pair product with the allocation modes of blsw_layout_multi_inputs; columns: 0 = one, then the inputs in that layout's order, then the
+ * witnesses. multi_inputs 0 = blsw_matrices_info / _fill (msg_len, 0, n_pairs) */
+int blsw_matrices_info_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, blsw_matrices_info_t* out);
+int blsw_matrices_fill_multi_inputs(uint32_t msg_len, uint32_t n_pairs, uint32_t multi_inputs, const blsw_matrices_info_t* info, blsw_matrices_t* out);
 
 /* Device R1CS evaluator (ABI 11): checks and evaluates the matrices above against witness vectors on the GPU — arkworks'
  * cs.is_satisfied() / cs.which_is_unsatisfied() and the A z, B z, C z a prover computes first, for n instances at a time.

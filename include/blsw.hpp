@@ -265,7 +265,8 @@ class ConstraintSystem {
     }
     // instance_assignment of system i after verify: n_instance_vars elements (element 0 = one; then the message chunks of UInt8::new_input_vec and
     // the coordinates of the points allocated with AllocationMode::Input, in allocation order), same element encoding as witness_assignment.
-    // After aggregate_verify with Input arguments: [1, the keys' x, y, z, the bitmap bits, the message chunks, the signature's six], the Input groups only
+    // After aggregate_verify with Input arguments: [1, the keys' x, y, z, the bitmap bits, the message chunks, the signature's six], the Input groups only.
+    // After verify_multi with Input arguments: [1, the message chunks pair by pair, the keys' x, y, z pair by pair, the signature's six], likewise
     std::vector<uint64_t> instance_assignment(size_t i) const {
         if (i >= n_) throw Error("instance_assignment out of range", BLSW_ERR_ARG);
         std::vector<uint64_t> v((size_t)layout_.n_instance_vars * 6);
@@ -299,7 +300,8 @@ class ConstraintSystem {
     detail::DeviceBytes r1cs_buffer_;
     blsw_matrices_info_t matrices_info() const {
         blsw_matrices_info_t info;
-        check(layout_.n_keys && agg_inputs_      ? blsw_matrices_info_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info)
+        check(layout_.n_pairs > 1                ? blsw_matrices_info_multi_inputs(msg_len_, layout_.n_pairs, multi_inputs_, &info)
+              : layout_.n_keys && agg_inputs_    ? blsw_matrices_info_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info)
               : msg_mode_                        ? blsw_matrices_info_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info)
               : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_info_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info)
               : layout_.params_mode              ? blsw_matrices_info_params(msg_len_, layout_.params_mode, &info)
@@ -320,7 +322,8 @@ class ConstraintSystem {
             m.col[k] = col[k].data();
             m.val[k] = val[k].data();
         }
-        check(layout_.n_keys && agg_inputs_      ? blsw_matrices_fill_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info, &m)
+        check(layout_.n_pairs > 1                ? blsw_matrices_fill_multi_inputs(msg_len_, layout_.n_pairs, multi_inputs_, &info, &m)
+              : layout_.n_keys && agg_inputs_    ? blsw_matrices_fill_aggregate_inputs(msg_len_, layout_.n_keys, agg_inputs_, &info, &m)
               : msg_mode_                        ? blsw_matrices_fill_inputs(msg_len_, 1, layout_.pk_mode, layout_.sig_mode, &info, &m)
               : layout_.pk_mode || layout_.sig_mode ? blsw_matrices_fill_io(msg_len_, layout_.pk_mode, layout_.sig_mode, &info, &m)
               : layout_.params_mode              ? blsw_matrices_fill_params(msg_len_, layout_.params_mode, &info, &m)
@@ -343,6 +346,7 @@ class ConstraintSystem {
     }
     uint32_t msg_mode_ = 0;  // the message allocated with UInt8::new_input_vec (its chunks are instance_assignment[1 .. c])
     uint32_t agg_inputs_ = 0;  // aggregate_verify: BLSW_AGG_*_INPUT of the circuit it synthesised (blsw_layout_aggregate_inputs)
+    uint32_t multi_inputs_ = 0;  // verify_multi: BLSW_MULTI_*_INPUT of the circuit it synthesised (blsw_layout_multi_inputs; layout_.n_pairs > 1)
     std::vector<int32_t> status_;
 };
 
@@ -481,7 +485,7 @@ struct BlsSignatureVerifyGadget {
         if (public_key.keys_.size() != n || signature.sigs_.size() != n || message.bytes().size() != n * cs.msg_len_)
             throw Error("verify: variables of another ConstraintSystem", BLSW_ERR_ARG);
         // one circuit shape per ConstraintSystem: aggregate_verify has replaced the layout (num_witness_variables would be the aggregate circuit's)
-        if (cs.layout_.n_keys) throw Error("verify: this ConstraintSystem was synthesised by aggregate_verify; use a new one", BLSW_ERR_ARG);
+        if (cs.layout_.n_keys || cs.layout_.n_pairs > 1) throw Error("verify: this ConstraintSystem was synthesised by aggregate_verify / verify_multi; use a new one", BLSW_ERR_ARG);
         if (message.is_input() != (cs.msg_mode_ == 1)) throw Error("verify: the message's AllocationMode is not the one of this ConstraintSystem's circuit", BLSW_ERR_ARG);
         if (!cs.engine_) {
             blsw_engine_options_t opt;
@@ -653,6 +657,92 @@ struct BlsSignatureVerifyGadget {
             b.v_[i] = r[i] == 1 && cs.status_[2 * i] == BLSW_ST_OK && cs.status_[2 * i + 1] == BLSW_ST_OK;
         }
         return {b, count};
+    }
+
+    // The N+1-pair product (blsw_layout_multi) for the n systems of `cs`: ONE signature over K (pk_j, msg_j) pairs per system; public_keys[j] /
+    // messages[j] hold key j / message j of every system. K >= 2, Constant parameters. The keys (all in one mode), the messages (all in one mode) and
+    // the signature may each be allocated as Input (PublicKeyVar / SignatureVar::new_variable(.., Input), UInt8::new_input_vec): the circuit is the
+    // one of blsw_layout_multi_inputs, and instance_assignment(i) holds the public inputs. Runs on an engine of blsw_engine_create_multi_inputs with options.n_pairs = K (one step per
+    // group, two group buffers). A key or a signature that does not decode to a non-identity subgroup point makes its system false (status(): the
+    // first such key's status, the signature's), as in verify. Synchronous.
+    static Boolean verify_multi(const ParametersVar& parameters, const std::vector<PublicKeyVar>& public_keys, const std::vector<MessageVar>& messages,
+                                const SignatureVar& signature) {
+        if (!parameters.cs_) throw Error("verify_multi: parameters were not allocated in a ConstraintSystem", BLSW_ERR_ARG);
+        ConstraintSystem& cs = *parameters.cs_;
+        const size_t n = cs.n_, K = public_keys.size();
+        if (K < 2 || messages.size() != K) throw Error("verify_multi: public_keys.len() == messages.len() >= 2", BLSW_ERR_ARG);
+        if (cs.layout_.params_mode || cs.engine_) throw Error("verify_multi: Constant parameters, a ConstraintSystem not used by verify", BLSW_ERR_ARG);
+        if (signature.sigs_.size() != n) throw Error("verify_multi: variables of another ConstraintSystem", BLSW_ERR_ARG);
+        for (size_t j = 0; j < K; j++) {
+            if (public_keys[j].keys_.size() != n || messages[j].bytes().size() != n * cs.msg_len_) throw Error("verify_multi: one key and one message per pair and system", BLSW_ERR_ARG);
+            if (public_keys[j].input_ != public_keys[0].input_ || messages[j].is_input() != messages[0].is_input())
+                throw Error("verify_multi: every key in one AllocationMode, every message in one AllocationMode", BLSW_ERR_ARG);
+        }
+        const uint32_t mask = (public_keys[0].input_ ? BLSW_MULTI_KEYS_INPUT : 0u) | (messages[0].is_input() ? BLSW_MULTI_MSG_INPUT : 0u) |
+                              (signature.input_ ? BLSW_MULTI_SIG_INPUT : 0u);
+        cs.multi_inputs_ = mask;
+        cs.msg_mode_ = 0;  // the product's modes are the mask
+        check(blsw_layout_multi_inputs(cs.msg_len_, (uint32_t)K, mask, &cs.layout_), "blsw_layout_multi_inputs");
+        if (cs.device_ >= 0) hip_check(hipSetDevice(cs.device_), "hipSetDevice");
+        // compressed inputs, system-major: keys [n][K][48], messages [n][K][msg_len], signatures [n][96]
+        const size_t m = n * K, len = cs.msg_len_;
+        std::vector<uint8_t> pk(m * 48), msg(m * len), sg(n * 96);
+        for (size_t j = 0; j < K; j++)
+            for (size_t i = 0; i < n; i++) {
+                std::memcpy(&pk[(i * K + j) * 48], public_keys[j].keys_[i].bytes.data(), 48);
+                if (len) std::memcpy(&msg[(i * K + j) * len], &messages[j].bytes()[i * len], len);
+            }
+        for (size_t i = 0; i < n; i++) std::memcpy(&sg[96 * i], signature.sigs_[i].bytes.data(), 96);
+        // decode (blsw_decode_batch takes as many keys as signatures: the keys with a block of zero bytes beside them, then the signatures likewise)
+        detail::DeviceBytes d_pk(m * 48), d_sg(m * 96), d_sg_xy(m * 192), d_st(m * 8), d_msg(msg.size());
+        cs.pk_xy_ = detail::DeviceBytes(m * 96);  // the step's inputs stay alive with the system
+        hip_check(hipMemset(d_sg.get(), 0, m * 96), "hipMemset");
+        d_pk.upload(pk.data(), pk.size());
+        check(blsw_decode_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), m, static_cast<uint64_t*>(cs.pk_xy_.get()),
+                                static_cast<uint64_t*>(d_sg_xy.get()), static_cast<int32_t*>(d_st.get()), nullptr),
+              "blsw_decode_batch");
+        std::vector<int32_t> st_keys(2 * m);
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        d_st.download(st_keys.data(), m * 8);
+        detail::DeviceBytes d_pk0(n * 48), d_sig(n * 96), d_pk0_xy(n * 96), d_st2(n * 8);
+        cs.sig_xy_ = detail::DeviceBytes(n * 192);
+        hip_check(hipMemset(d_pk0.get(), 0, n * 48), "hipMemset");
+        d_sig.upload(sg.data(), sg.size());
+        check(blsw_decode_batch(static_cast<const uint8_t*>(d_pk0.get()), static_cast<const uint8_t*>(d_sig.get()), n, static_cast<uint64_t*>(d_pk0_xy.get()),
+                                static_cast<uint64_t*>(cs.sig_xy_.get()), static_cast<int32_t*>(d_st2.get()), nullptr),
+              "blsw_decode_batch");
+        std::vector<int32_t> st_sig(2 * n);
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        d_st2.download(st_sig.data(), n * 8);
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        blsw_engine_options_t opt;
+        check(blsw_engine_options_default(&opt), "blsw_engine_options_default");
+        opt.device = cs.device_;
+        opt.n_pairs = (uint32_t)K;
+        uint64_t bytes = 0;
+        check(blsw_engine_workspace_bytes_multi_inputs(n, cs.msg_len_, 1, 2, &opt, mask, &bytes), "blsw_engine_workspace_bytes_multi_inputs");
+        cs.workspace_ = detail::DeviceBytes(bytes);
+        cs.witness_ = detail::DeviceBytes(n * (size_t)cs.layout_.n_witness * 48);
+        cs.instance_ = detail::DeviceBytes(n * (size_t)cs.layout_.n_instance_vars * 48);
+        cs.result_ = detail::DeviceBytes(n * 4);
+        check(blsw_engine_create_multi_inputs(&cs.engine_, n, cs.msg_len_, 1, 2, &opt, mask, cs.workspace_.get(), bytes), "blsw_engine_create_multi_inputs");
+        check(blsw_engine_submit_multi_io(cs.engine_, static_cast<const uint64_t*>(cs.pk_xy_.get()), static_cast<const uint8_t*>(d_msg.get()),
+                                          static_cast<const uint64_t*>(cs.sig_xy_.get()), static_cast<uint64_t*>(cs.instance_.get()),
+                                          static_cast<uint64_t*>(cs.witness_.get()), cs.layout_.n_witness, static_cast<int32_t*>(cs.result_.get()), nullptr),
+              "blsw_engine_submit_multi_io");
+        check(blsw_engine_flush(cs.engine_, nullptr), "blsw_engine_flush");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n);
+        cs.result_.download(r.data(), n * 4);
+        cs.status_.assign(2 * n, BLSW_ST_OK);
+        Boolean b;
+        b.v_.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            for (size_t j = 0; j < K && cs.status_[2 * i] == BLSW_ST_OK; j++) cs.status_[2 * i] = st_keys[2 * (i * K + j)];
+            cs.status_[2 * i + 1] = st_sig[2 * i + 1];
+            b.v_[i] = r[i] == 1 && cs.status_[2 * i] == BLSW_ST_OK && cs.status_[2 * i + 1] == BLSW_ST_OK;
+        }
+        return b;
     }
 };
 
