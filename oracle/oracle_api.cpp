@@ -234,6 +234,21 @@ void orc_expand(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_l
     std::vector<U8> r = hasher_expand(m, d, len_in_bytes);
     for (size_t i = 0; i < len_in_bytes; i++) out[i] = r[i].value();
 }
+// the "hash.expand" segment alone: the message allocated as witness bytes (as the circuit does before it), then hasher_expand with the
+// circuit's DST and 256 output bytes, without the rest of the circuit. bits [cap]: one byte per witness the expansion allocates, in allocation
+// order (0 / 1; 2 for a value that is no boolean); uniform [256]. Returns the segment's length, whatever cap is.
+uint64_t orc_hash_expand(const uint8_t* msg, size_t len, uint8_t* bits, uint64_t cap, uint8_t* uniform) {
+    ValueScope s;
+    std::vector<U8> m = u8witness_vec(msg, len);
+    std::vector<U8> d = u8const_vec((const uint8_t*)BLS_DST, strlen(BLS_DST));
+    const size_t start = s.cs.wit.size();
+    std::vector<U8> r = hasher_expand(m, d, 256);
+    const size_t n = s.cs.wit.size() - start;
+    for (size_t i = 0; i < n && i < cap; i++) bits[i] = fp_is_zero(s.cs.wit[start + i]) ? 0 : (fp_eq(s.cs.wit[start + i], fp_one()) ? 1 : 2);
+    if (uniform)
+        for (size_t i = 0; i < 256; i++) uniform[i] = r[i].value();
+    return n;
+}
 // tests/tests.rs:239-268 semantics: undecodable key/signature fall back to the identity; any Err => false
 int orc_verify_bytes(const uint8_t* pk, size_t pk_len, const uint8_t* msg, size_t len, const uint8_t* sig, size_t sig_len) {
     G1Aff p = {fp_zero(), fp_zero(), true};

@@ -18,6 +18,7 @@
 #include "../devfield/ops.hpp"
 #include "../devteam/ops.hpp"
 #include "../devcurve/ops.hpp"
+#include "../devsha/ops.hpp"
 #include <array>
 
 using namespace blsw;
@@ -835,5 +836,74 @@ int64_t hostsim_sink_script(const uint32_t* script, uint32_t n_ops, const uint32
     s.flush();
     *nbits = s.nbits;
     return (int64_t)s.widx;
+}
+// one entry of the SHA gadget table (tests/devsha/ops.hpp: the table tests/devsha/devsha.hip runs on the device) on one item: in
+// [DEVSHA_IN_MAX] u32 operands, msg [msg_len], out [DEVSHA_OUT_MAX] u32 (the entry's own count written), words [cap] the entry's bit stream through
+// sha.hpp's host BitSink (flushed), *nbits its bit count. Returns the word count, -1 for an unknown entry, -2 when the stream does not fit cap
+// (the entry is run on a counting sink first).
+int64_t hostsim_sha_op(int op, const uint32_t* in, const uint8_t* msg, uint32_t msg_len, uint32_t* out, uint32_t* words, uint64_t cap, uint64_t* nbits) {
+    uint32_t scratch[DEVSHA_OUT_MAX];
+    for (int pass = 0; pass < 2; pass++) {
+        BitSink s;
+        s.init(pass ? words : nullptr, 1);
+        uint32_t* o = pass ? out : scratch;
+        switch (op) {
+#define HOSTSIM_X_SRUN(name, n_in, n_out, m, fl)                          \
+    case devsha::OP_##name:                                               \
+        devsha::ShaOp<devsha::OP_##name>::run(in, msg, msg_len, o, s);    \
+        break;
+            DEVSHA_OPS(HOSTSIM_X_SRUN)
+#undef HOSTSIM_X_SRUN
+            default:
+                return -1;
+        }
+        if (!devsha::op_flushes(op)) s.flush();
+        if (!pass && (s.nbits + 31) / 32 > cap) return -2;
+        if (pass) {
+            *nbits = s.nbits;
+            return (int64_t)s.widx;
+        }
+    }
+    return -1;
+}
+// the same over n items: in [n][DEVSHA_IN_MAX], msg [n][msg_len], out [n][DEVSHA_OUT_MAX], words [n][cap], nwords [n], nbits [n]
+int hostsim_sha_op_batch(int op, uint64_t n, const uint32_t* in, const uint8_t* msg, uint32_t msg_len, uint32_t* out, uint32_t* words, uint64_t cap, uint32_t* nwords,
+                         uint64_t* nbits) {
+    if (devsha::op_n_out(op) < 0) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+        const int64_t r = hostsim_sha_op(op, in + i * DEVSHA_IN_MAX, msg + i * (uint64_t)msg_len, msg_len, out + i * DEVSHA_OUT_MAX, words + i * cap, cap, nbits + i);
+        if (r < 0) return (int)r;
+        nwords[i] = (uint32_t)r;
+    }
+    return 0;
+}
+const char* hostsim_sha_op_name(int op) {
+    static const char* const T[devsha::OP_COUNT] = {
+#define HOSTSIM_X_SNAME(name, n_in, n_out, m, fl) #name,
+        DEVSHA_OPS(HOSTSIM_X_SNAME)
+#undef HOSTSIM_X_SNAME
+    };
+    return (op >= 0 && op < devsha::OP_COUNT) ? T[op] : "";
+}
+int hostsim_sha_op_count() { return devsha::OP_COUNT; }
+int hostsim_sha_op_n_in(int op) { return devsha::op_n_in(op); }
+int hostsim_sha_op_n_out(int op) { return devsha::op_n_out(op); }
+int hostsim_sha_op_msg(int op) { return devsha::op_msg(op); }
+// the "hash.expand" segment of one message alone, as hostsim_witness_params emits it: bits [cap] one byte per boolean witness in allocation
+// order, uniform [256] the bytes of b1 .. b8. Returns the segment's length (the layout's sha_bits), -1 when it differs from the layout's or
+// does not fit cap.
+int64_t hostsim_hash_expand(const uint8_t* msg, uint32_t msg_len, uint8_t* bits, uint64_t cap, uint8_t* uniform) {
+    blsw_layout_t L;
+    make_layout(msg_len, &L);
+    std::vector<uint32_t> w((L.sha_bits + 31) / 32 + 1, 0);
+    BitSink s;
+    s.init(w.data(), 1);
+    uint32_t uw[64];
+    expand_message_w(s, msg, msg_len, false, uw);
+    if (s.nbits != L.sha_bits || s.nbits > cap) return -1;
+    for (uint32_t i = 0; i < L.sha_bits; i++) bits[i] = (w[i >> 5] >> (i & 31)) & 1;
+    for (int i = 0; i < 64; i++)
+        for (int b = 0; b < 4; b++) uniform[4 * i + b] = (uint8_t)(uw[i] >> (8 * (3 - b)));
+    return (int64_t)L.sha_bits;
 }
 }

@@ -92,6 +92,17 @@ class Oracle:
         self.lib.orc_expand(self._buf(msg), ctypes.c_size_t(len(msg)), self._buf(dst), ctypes.c_size_t(len(dst)), ctypes.c_size_t(n), out)
         return bytes(out)
 
+    def hash_expand(self, msg):
+        """the oracle's "hash.expand" segment alone (the message as witness bytes, the circuit's DST, 256 bytes) -> (bits uint8 [n] in allocation
+        order, uniform bytes); the rest of the circuit is not run"""
+        self.lib.orc_hash_expand.restype = ctypes.c_uint64
+        uni = (ctypes.c_uint8 * 256)()
+        cap = 45000 * ((len(msg) + 183) // 64 + 16)  # above the ~41 k witnesses of a fully live block (SURVEY App. A.4)
+        bits = np.zeros(cap, dtype=np.uint8)
+        n = self.lib.orc_hash_expand(self._buf(msg), ctypes.c_size_t(len(msg)), bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.c_uint64(cap), uni)
+        assert n <= cap
+        return bits[:n].copy(), bytes(uni)
+
     def verify_bytes(self, pk, msg, sig):
         return bool(
             self.lib.orc_verify_bytes(self._buf(pk), ctypes.c_size_t(len(pk)), self._buf(msg), ctypes.c_size_t(len(msg)), self._buf(sig), ctypes.c_size_t(len(sig)))
