@@ -46,7 +46,17 @@ class blsw_compact_layout_t(ctypes.Structure):
                [(n, ctypes.c_uint32) for n in "n_witness off_expand sha_bits sha_words split_row staging_rows pair_rows moved_lo moved_len moved_at".split()]
 
 
+class blsw_compact_layout_multi_t(ctypes.Structure):
+    """where the witnesses of a step of the N+1-pair product live in its compact buffer: bit words and pair tiles by pair lane i * n_pairs + j,
+    instance tiles, instance rows (include/blsw.h)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in "n off_staging off_inst off_pair total".split()] + \
+               [(n, ctypes.c_uint32) for n in "n_pairs n_witness sha_bits sha_words off_expand stride_hash rows_p rows_i pair_rows inst_tile_w off_miller reserved".split()] + \
+               [(n, ctypes.c_uint32 * 6) for n in "pair_run_row pair_run_off pair_run_stride pair_run_len".split()] + \
+               [(n, ctypes.c_uint32 * 2) for n in "inst_run_row inst_run_off inst_run_len".split()]
+
+
 COMPACT_BIT, COMPACT_TILE, COMPACT_PAIR = 0, 1, 2  # regions of compact_locate
+COMPACT_INST = 3  # compact_locate_multi: an instance tile (COMPACT_TILE: a pair tile, COMPACT_PAIR: the instance rows)
 
 ERR_BUSY = 6
 
@@ -168,6 +178,15 @@ def lib():
         L.blsw_r1cs_check_keyset.argtypes = [vp, vp, vp, vp, vp]
         L.blsw_r1cs_check_compact_keyset.argtypes = [vp, cl, vp, vp, u32, vp, u64, vp, vp, vp]
         L.blsw_r1cs_evaluate_compact_keyset.argtypes = [vp, cl, vp, vp, vp, u64, u64, u64, vp, vp, vp, vp]
+        cm = ctypes.POINTER(blsw_compact_layout_multi_t)
+        L.blsw_compact_layout_multi.argtypes = [u64, u32, ctypes.POINTER(blsw_engine_options_t), u32, cm]
+        L.blsw_compact_locate_multi.argtypes = [cm, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.blsw_compact_locate_multi_range.argtypes = [cm, u32, u32, u64, vp, vp, vp]
+        L.blsw_r1cs_pair_families.argtypes = [mi, mp, cm, u64, vp, vp, ctypes.POINTER(u64)]
+        L.blsw_r1cs_handle_pair_families.argtypes = [vp, cm, u64, vp, vp, ctypes.POINTER(u64)]
+        L.blsw_r1cs_check_compact_multi.argtypes = [vp, cm, vp, vp, u64, vp, vp, vp]
+        L.blsw_r1cs_check_compact_multi_ex.argtypes = [vp, cm, vp, vp, u64, u32, vp, vp, vp]
+        L.blsw_r1cs_evaluate_compact_multi.argtypes = [vp, cm, vp, vp, u64, u64, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -185,7 +204,9 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_keyset_broadcast_rate", "blsw_engine_submit_aggregate_keyset", "blsw_engine_submit_aggregate_keyset_compact",
                     "blsw_engine_expand_compact_keyset", "blsw_compact_layout_keyset", "blsw_r1cs_head_rows", "blsw_r1cs_handle_head_rows", "blsw_r1cs_check_keyset",
                     "blsw_r1cs_check_compact_keyset", "blsw_r1cs_evaluate_compact_keyset", "blsw_layout_multi_inputs", "blsw_matrices_info_multi_inputs",
-                    "blsw_matrices_fill_multi_inputs", "blsw_engine_submit_multi_io", "blsw_engine_workspace_bytes_multi_inputs", "blsw_engine_create_multi_inputs"]
+                    "blsw_matrices_fill_multi_inputs", "blsw_engine_submit_multi_io", "blsw_engine_workspace_bytes_multi_inputs", "blsw_engine_create_multi_inputs",
+                    "blsw_compact_layout_multi", "blsw_compact_locate_multi", "blsw_compact_locate_multi_range", "blsw_r1cs_pair_families",
+                    "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -330,6 +351,38 @@ def compact_locate_all(layout, lane):
         if fn(lp, k, lane, rp, op, bp):
             raise BlswError("blsw_compact_locate failed at k = %d" % k)
         region[k], off[k], bit[k] = r.value, o.value, b.value
+    return region, off, bit
+
+
+def compact_layout_multi(n, msg_len=32, n_pairs=None, multi_inputs=0, **options):
+    """blsw_compact_layout_multi: where every witness element of a compact step of n instances of the N+1-pair product lives
+    (blsw_compact_layout_multi_t), for the engine arguments given as in WitnessEngine(..., n_pairs=K, multi_inputs=mask). Host only."""
+    opt = options.pop("_opt", None) or engine_options(n_pairs=n_pairs, **options)
+    c = blsw_compact_layout_multi_t()
+    rc = lib().blsw_compact_layout_multi(n, msg_len, ctypes.byref(opt), multi_inputs, ctypes.byref(c))
+    if rc:
+        raise BlswError("blsw_compact_layout_multi failed: %d" % rc)
+    return c
+
+
+def compact_locate_multi(layout, k, instance):
+    """blsw_compact_locate_multi -> (region COMPACT_BIT / _TILE / _INST / _PAIR, byte offset in the buffer, bit position in the u32 word at that offset)"""
+    region, off, bit = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    rc = lib().blsw_compact_locate_multi(ctypes.byref(layout), k, instance, ctypes.byref(region), ctypes.byref(off), ctypes.byref(bit))
+    if rc:
+        raise BlswError("blsw_compact_locate_multi failed: %d" % rc)
+    return region.value, off.value, bit.value
+
+
+def compact_locate_multi_all(layout, instance, k_begin=0, count=None):
+    """compact_locate_multi of witnesses [k_begin, k_begin + count) (default: all) of one instance -> (region uint8, byte offset uint64, bit uint8)"""
+    import numpy as np
+
+    count = layout.n_witness - k_begin if count is None else count
+    region, off, bit = np.empty(count, np.uint8), np.empty(count, np.uint64), np.empty(count, np.uint8)
+    rc = lib().blsw_compact_locate_multi_range(ctypes.byref(layout), k_begin, count, instance, region.ctypes.data, off.ctypes.data, bit.ctypes.data)
+    if rc:
+        raise BlswError("blsw_compact_locate_multi_range failed: %d" % rc)
     return region, off, bit
 
 
@@ -609,6 +662,8 @@ class WitnessEngine:
         engine: the layout of the buffer alone (compact_layout_keyset; the head is the step's KeySet, passed to the checker as keyset=)."""
         if self._opt.shared_keys:
             return compact_layout_keyset(self.n, self.msg_len, _opt=self._opt)[0]
+        if self.n_pairs > 1:  # the N+1-pair product: blsw_compact_layout_multi_t, which the same checker calls take
+            return compact_layout_multi(self.n, self.msg_len, multi_inputs=self.multi_inputs, _opt=self._opt)
         return compact_layout(self.n, self.msg_len, _opt=self._opt)
 
     def new_compact_buffer(self, batches=1):
@@ -1234,6 +1289,28 @@ def r1cs_head_rows(mats, head_len):
     return rows.value
 
 
+def _pair_families(call, layout):
+    assert isinstance(layout, blsw_compact_layout_multi_t)
+    import numpy as np
+
+    count = ctypes.c_uint64(0)
+    rc = call(ctypes.byref(layout), 0, None, None, ctypes.byref(count))
+    if rc:
+        raise BlswError("blsw_r1cs_pair_families failed: %d" % rc)
+    first, rows = np.zeros(max(count.value, 1), np.uint64), np.zeros(max(count.value, 1), np.uint64)
+    rc = call(ctypes.byref(layout), count.value, first.ctypes.data, rows.ctypes.data, ctypes.byref(count))
+    if rc:
+        raise BlswError("blsw_r1cs_pair_families failed: %d" % rc)
+    return [(int(f), int(r)) for f, r in zip(first[:count.value], rows[:count.value])]
+
+
+def r1cs_pair_families(mats, layout):
+    """blsw_r1cs_pair_families: the pair families [(first_row, rows_per_pair)] of a matrices() dict under a blsw_compact_layout_multi_t — runs of
+    n_pairs consecutive blocks that are translated copies of the first, entry for entry (host only; validates the CSR like r1cs_device_bytes)"""
+    info, m = _matrices_struct(mats)
+    return _pair_families(lambda *a: lib().blsw_r1cs_pair_families(ctypes.byref(info), ctypes.byref(m), *a), layout)
+
+
 class ConstraintChecker:
     """The constraint system of one circuit shape on the GPU (blsw_r1cs_*): arkworks' cs.is_satisfied() / cs.which_is_unsatisfied() and the
     A z, B z, C z rows, for a batch of witness vectors at once. Arguments as matrices(). Inputs are the tensors WitnessEngine writes:
@@ -1366,7 +1443,7 @@ class ConstraintChecker:
     def _io_compact(self, layout, compact, instance, stream, keyset=None):
         """-> (n, instance pointer, instance stride, stream) for a step's compact buffer (uint8 cuda tensor of layout.total bytes)"""
         torch = self.torch
-        assert isinstance(layout, blsw_compact_layout_t)
+        assert isinstance(layout, (blsw_compact_layout_t, blsw_compact_layout_multi_t))
         assert keyset is None or (isinstance(keyset, KeySet) and keyset.device == self.device)
         assert compact.is_cuda and compact.device == self.device and compact.is_contiguous() and compact.dtype.itemsize == 1 and compact.numel() >= layout.total
         n, ip, ist = int(layout.n), None, 0
@@ -1383,7 +1460,24 @@ class ConstraintChecker:
                 keyset.buffer.record_stream(s)
         return n, ip, ist, s
 
-    def _check_compact(self, layout, compact, instance, stream, want_unreduced, keyset=None, skip_head_rows=False):
+    def pair_families(self, layout):
+        """the pair families of this system under a blsw_compact_layout_multi_t: [(first_row, rows_per_pair)], the blocks the compact check of an
+        N+1-pair step evaluates with one pair per lane (blsw_r1cs_handle_pair_families; computed once per layout, the first call synchronises)"""
+        return _pair_families(lambda *a: lib().blsw_r1cs_handle_pair_families(self._r, *a), layout)
+
+    def _check_compact(self, layout, compact, instance, stream, want_unreduced, keyset=None, skip_head_rows=False, _use_families=True):
+        if isinstance(layout, blsw_compact_layout_multi_t):
+            if keyset is not None or skip_head_rows:
+                raise BlswError("keyset= / skip_head_rows belong to a shared-keys aggregate step, not to the N+1-pair product")
+            n, ip, ist, s = self._io_compact(layout, compact, instance, stream)
+            with self.torch.cuda.stream(s):
+                bad = self.torch.empty(n, dtype=self.torch.int64, device=self.device)
+                unr = self.torch.empty(n, dtype=self.torch.int64, device=self.device) if want_unreduced else None
+            rc = lib().blsw_r1cs_check_compact_multi_ex(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, 1 if _use_families else 0, bad.data_ptr(),
+                                                        unr.data_ptr() if unr is not None else None, s.cuda_stream)
+            if rc:
+                raise BlswError("blsw_r1cs_check_compact_multi failed: %d" % rc)
+            return bad, unr
         if keyset is None and skip_head_rows:
             raise BlswError("skip_head_rows needs keyset=: only a shared-keys step has head rows to skip")
         n, ip, ist, s = self._io_compact(layout, compact, instance, stream, keyset)
@@ -1422,12 +1516,16 @@ class ConstraintChecker:
         which_is_unsatisfied_compact; any row window, head rows included (skip_head_rows has nothing to skip here and must stay False)."""
         if skip_head_rows:
             raise BlswError("evaluate_compact evaluates the window it is given: skip_head_rows does not apply")
+        if isinstance(layout, blsw_compact_layout_multi_t) and keyset is not None:
+            raise BlswError("keyset= belongs to a shared-keys aggregate step, not to the N+1-pair product")
         begin, count = rows if rows is not None else (0, self.n_constraints)
         n, ip, ist, s = self._io_compact(layout, compact, instance, stream, keyset)
         with self.torch.cuda.stream(s):
             out = [self.torch.empty((n, count, 6), dtype=self.torch.int64, device=self.device) for _ in range(3)]
         outs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), s.cuda_stream)
-        if keyset is not None:
+        if isinstance(layout, blsw_compact_layout_multi_t):
+            rc = lib().blsw_r1cs_evaluate_compact_multi(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, begin, count, *outs)
+        elif keyset is not None:
             rc = lib().blsw_r1cs_evaluate_compact_keyset(self._r, ctypes.byref(layout), compact.data_ptr(), keyset._ks, ip, ist, begin, count, *outs)
         else:
             rc = lib().blsw_r1cs_evaluate_compact(self._r, ctypes.byref(layout), compact.data_ptr(), ip, ist, begin, count, *outs)

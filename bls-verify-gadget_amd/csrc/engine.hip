@@ -1006,6 +1006,33 @@ int blsw_compact_locate(const blsw_compact_layout_t* layout, uint32_t k, uint64_
     *region = compact_locate(*layout, k, lane, byte_offset, bit);
     return BLSW_OK;
 }
+// the compact steps of a staged N+1-pair engine of these arguments (pair tiles, instance tiles, instance rows), described for a consumer
+// (blsw_r1cs_check_compact_multi); host only
+int blsw_compact_layout_multi(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, uint32_t multi_inputs, blsw_compact_layout_multi_t* out) {
+    if (!out || !options || options->n_pairs < 2) return BLSW_ERR_ARG;
+    if (int rc = check_options(n, msg_len, 2, 1, options, multi_inputs)) return rc;  // any staged engine, as blsw_compact_layout
+    if (!compact_shape_ok(n, options->n_pairs)) return BLSW_ERR_ARG;
+    blsw_layout_t L;
+    options_layout(msg_len, options, multi_inputs, &L);
+    *out = compact_layout_multi(n, L);
+    return BLSW_OK;
+}
+int blsw_compact_locate_multi(const blsw_compact_layout_multi_t* layout, uint32_t k, uint64_t instance, uint32_t* region, uint64_t* byte_offset, uint32_t* bit) {
+    if (!layout || !region || !byte_offset || !bit || !compact_layout_multi_ok(*layout) || k >= layout->n_witness || instance >= layout->n) return BLSW_ERR_ARG;
+    *region = compact_locate_multi(*layout, k, instance, byte_offset, bit);
+    return BLSW_OK;
+}
+int blsw_compact_locate_multi_range(const blsw_compact_layout_multi_t* layout, uint32_t k_begin, uint32_t count, uint64_t instance, uint8_t* regions, uint64_t* byte_offsets,
+                                    uint8_t* bits) {
+    if (!layout || !regions || !byte_offsets || !bits || !compact_layout_multi_ok(*layout) || instance >= layout->n) return BLSW_ERR_ARG;
+    if (k_begin > layout->n_witness || count > layout->n_witness - k_begin) return BLSW_ERR_ARG;
+    for (uint32_t t = 0; t < count; t++) {
+        uint32_t bit;
+        regions[t] = (uint8_t)compact_locate_multi(*layout, k_begin + t, instance, byte_offsets + t, &bit);
+        bits[t] = (uint8_t)bit;
+    }
+    return BLSW_OK;
+}
 int blsw_engine_submit_compact(blsw_engine_t* e, const uint64_t* d_pk_xy, const uint64_t* d_sig_xy, const uint8_t* d_msg, void* d_compact, int32_t* d_result,
                                void* stream_) {
     if (!e || e->L.n_keys || e->L.n_pairs > 1 || !e->staged || e->n % 64 || !d_compact || !d_pk_xy || !d_sig_xy || (!d_msg && e->msg_len)) return BLSW_ERR_ARG;

@@ -22,10 +22,18 @@
 // is one address for all 64 lanes — wave-uniform like the column itself, so the fourth branch does not diverge either. The leading rows that read
 // nothing but the head (head_cover, r1cs_encode.hpp) are a function of the committee alone: blsw_r1cs_check_keyset evaluates them once per set
 // (the plain kernel, one instance whose witness vector is the table) and the step's check may then start at the first row behind them.
+// A step of the N+1-pair product (blsw_compact_layout_multi_t: bit words and pair tiles by pair lane i K + j, instance tiles, instance rows) has
+// few instances — n K <= 65535 — so one instance per lane leaves most of a wave idle and walks all K copies of the per-pair rows. Two sources: the
+// general one (MultiCompactArgs, the k_r1cs template, compact_place_multi / compact_address_multi per entry) for the evaluation and for the rows of
+// the check outside the pair families; and k_r1cs_pairs, lane = PAIR lane, over the one template block of each family (pair_families,
+// r1cs_encode.hpp: K consecutive blocks that are translated copies of the first, verified entry by entry) — whole tile rows whatever n is, the
+// template's entries read once, a failing template row t of pair j reported as t + j R by atomicMin.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
+#include <mutex>
 #include <vector>
 #include "../../include/blsw.h"
 #include "kcommon.hpp"
@@ -69,6 +77,18 @@ struct KeysetCompactArgs : CompactArgs {
     uint32_t head_len;
 };
 
+// z from a compact step of the N+1-pair product (blsw_compact_layout_multi_t), one INSTANCE per lane: the general source — every row of the
+// evaluation, and the rows of the check that belong to no pair family
+struct MultiCompactArgs : Args {
+    blsw_compact_layout_multi_t c;
+    const char* compact;
+};
+// ... one PAIR per lane: the template block of a pair family (r1cs_encode.hpp: pair_families). The template's columns are column 0 and witnesses of
+// pair 0, i.e. a (region, row) of the bit words or the pair tiles; lane p reads the same (region, row) in its own column
+struct PairArgs : MultiCompactArgs {
+    uint64_t fam_rows;  // R: template row t of pair j is matrix row t + j * R
+};
+
 __device__ __forceinline__ Fp load_fp(const uint64_t* src) {
     const uint4* q = reinterpret_cast<const uint4*>(src);
     const uint4 a = q[0], b = q[1], c = q[2];
@@ -108,9 +128,45 @@ __device__ __forceinline__ Fp load_z(const KeysetCompactArgs& a, uint64_t i, uin
     return a.one;
 }
 
+// (region, row, bit) of a multi step for `lane` (a pair lane for BIT / TILE, an instance otherwise)
+__device__ __forceinline__ Fp load_multi(const MultiCompactArgs& a, uint32_t region, uint32_t row, uint32_t bit, uint64_t lane) {
+    const uint64_t off = compact_address_multi(a.c, region, row, lane);
+    if (region != BLSW_COMPACT_BIT) return load_fp(reinterpret_cast<const uint64_t*>(a.compact + off));
+    const uint32_t m = 0u - ((*reinterpret_cast<const uint32_t*>(a.compact + off) >> bit) & 1u);
+    Fp r;
+#pragma unroll
+    for (int j = 0; j < 12; j++) r.l[j] = a.one.l[j] & m;
+    return r;
+}
+__device__ __forceinline__ Fp load_z(const MultiCompactArgs& a, uint64_t i, uint32_t col) {
+    if (col >= a.n_inst) {
+        uint32_t j, row, bit;
+        const uint32_t region = compact_place_multi(a.c, col - a.n_inst, &j, &row, &bit);  // wave-uniform
+        if (region == BLSW_COMPACT_NONE) return fp_zero();                                  // (no struct compact_layout_multi_ok accepts gets here)
+        return load_multi(a, region, row, bit, region <= BLSW_COMPACT_TILE ? i * a.c.n_pairs + j : i);
+    }
+    if (a.inst) return load_fp(a.inst + (i * a.inst_stride + col) * 6);
+    return a.one;
+}
+// lane = pair lane p of instance i = p / K (computed once per lane, at kernel entry); a column of the template that is no pair-local witness cannot
+// occur (pair_families) and reads as zero
+struct PairLane {
+    uint64_t p, i;
+};
+__device__ __forceinline__ Fp load_z(const PairArgs& a, const PairLane& l, uint32_t col) {
+    if (col >= a.n_inst) {
+        uint32_t j, row, bit;
+        const uint32_t region = compact_place_multi(a.c, col - a.n_inst, &j, &row, &bit);
+        if (region > BLSW_COMPACT_TILE) return fp_zero();
+        return load_multi(a, region, row, bit, l.p);
+    }
+    if (a.inst) return load_fp(a.inst + (l.i * a.inst_stride + col) * 6);
+    return a.one;
+}
+
 // REDC(<M_row, z>) of one matrix row
-template <class A>
-__device__ __forceinline__ Fp row_dot(const A& a, int m, uint64_t k0, uint64_t k1, uint64_t i) {
+template <class A, class Lane>
+__device__ __forceinline__ Fp row_dot(const A& a, int m, uint64_t k0, uint64_t k1, const Lane& i) {
     Acc x;
 #pragma unroll
     for (int j = 0; j < 14; j++) x.l[j] = 0;
@@ -159,6 +215,36 @@ __global__ __launch_bounds__(64 * WAVES) void k_r1cs(A a) {
     if (!EVAL && bad != ~0ull) atomicMin(reinterpret_cast<unsigned long long*>(a.bad + i), (unsigned long long)bad);
 }
 
+// The template block of a pair family, one pair per lane: grid (row blocks of the template / 4, pair tiles n K / 64). Column and code stay wave-uniform;
+// a staged row is one contiguous 3 KB read per wave whatever n is, and the template's entries are read once, not once per pair. Template row t fails
+// for pair j of instance i: matrix row t + j R, by atomicMin into bad[i] — with the other pairs and the general path's rows, the matrix's first row.
+__global__ __launch_bounds__(64 * WAVES) void k_r1cs_pairs(PairArgs a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t b = blockIdx.x * WAVES + wave;
+    const uint64_t p = (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);  // n K is a multiple of 64: every lane is a pair
+    if (b >= a.n_blk) return;
+    const PairLane lane = {p, (uint64_t)((uint32_t)p / a.c.n_pairs)};  // n K <= 65535
+    const uint32_t blk = a.blk_first + b;
+    uint64_t r0 = a.e.blk[blk], r1 = a.e.blk[blk + 1];
+    r0 = r0 > a.row_lo ? r0 : a.row_lo;
+    r1 = r1 < a.row_hi ? r1 : a.row_hi;
+    uint64_t bad = ~0ull;
+#pragma unroll 1
+    for (uint64_t row = r0; row < r1; row++) {
+        const uint64_t a0 = a.e.rp[0][row], a1 = a.e.rp[0][row + 1], b0 = a.e.rp[1][row], b1 = a.e.rp[1][row + 1];
+        const uint64_t c0 = a.e.rp[2][row], c1 = a.e.rp[2][row + 1];
+        const Fp fa = a0 < a1 ? row_dot(a, 0, a0, a1, lane) : fp_zero();
+        const Fp fb = b0 < b1 ? row_dot(a, 1, b0, b1, lane) : fp_zero();
+        const Fp fc = c0 < c1 ? row_dot(a, 2, c0, c1, lane) : fp_zero();
+        const Fp lhs = (a0 < a1 && b0 < b1) ? fp_mul(fp_mul(fa, fb), a.k) : fp_zero();
+        if (!fp_eq(lhs, fc) && bad == ~0ull) bad = row;
+    }
+    if (bad != ~0ull) {
+        const uint64_t i = lane.i, j = p - i * a.c.n_pairs;
+        atomicMin(reinterpret_cast<unsigned long long*>(a.bad + i), (unsigned long long)(bad + j * a.fam_rows));
+    }
+}
+
 // first index k of z with z_k >= p: grid (chunks, instances of this slice); a thread's indices ascend, so its first hit is its minimum
 __global__ __launch_bounds__(256) void k_r1cs_unreduced(const uint64_t* __restrict__ inst, uint64_t inst_stride, const uint64_t* __restrict__ wit,
                                                         uint64_t wit_stride, uint32_t n_inst, uint64_t n_z, unsigned long long* __restrict__ out) {
@@ -199,6 +285,37 @@ __global__ __launch_bounds__(256) void k_r1cs_unreduced_compact(blsw_compact_lay
     }
 }
 
+// ... of the N+1-pair product, one region per launch. part 0: the pair tiles, grid (chunks, n K / 64), lane = pair lane, a wave takes a staged row at
+// a time; part 1: the instance tiles, grid (chunks, ceil(n / 64)), lane = instance; part 2: the instance rows, grid (chunks, n), a thread per element.
+// Every hit goes to the atomic, at base + the element's witness index (the inverse of compact_place_multi, run by run).
+__global__ __launch_bounds__(256) void k_r1cs_unreduced_multi(blsw_compact_layout_multi_t c, const char* __restrict__ compact, uint32_t base, uint32_t part,
+                                                              unsigned long long* __restrict__ out) {
+    constexpr uint32_t P[12] = BLSW_P_LIMBS;
+    const bool rows_major = part == 2;
+    const uint64_t lane = rows_major ? blockIdx.y : (uint64_t)blockIdx.y * 64 + (threadIdx.x & 63);
+    const uint32_t rows = part == 0 ? c.rows_p : part == 1 ? c.rows_i : c.pair_rows;
+    if (lane >= (part == 0 ? c.n * c.n_pairs : c.n)) return;
+    const uint64_t i = part == 0 ? lane / c.n_pairs : lane;
+    const uint32_t j = part == 0 ? (uint32_t)(lane - i * c.n_pairs) : 0u;
+    const uint32_t e0 = rows_major ? blockIdx.x * 256 + threadIdx.x : blockIdx.x * 4 + (threadIdx.x >> 6), step = rows_major ? gridDim.x * 256 : gridDim.x * 4;
+#pragma unroll 1
+    for (uint32_t e = e0; e < rows; e += step) {
+        uint32_t k = c.off_miller + e;
+        if (part == 0) {
+            for (int r = 0; r < 6; r++)
+                if (e >= c.pair_run_row[r] && e - c.pair_run_row[r] < c.pair_run_len[r]) k = c.pair_run_off[r] + j * c.pair_run_stride[r] + (e - c.pair_run_row[r]);
+        } else if (part == 1) {
+            for (int r = 0; r < 2; r++)
+                if (e >= c.inst_run_row[r] && e - c.inst_run_row[r] < c.inst_run_len[r]) k = c.inst_run_off[r] + (e - c.inst_run_row[r]);
+        }
+        const Fp z = load_fp(reinterpret_cast<const uint64_t*>(compact + compact_address_multi(c, part == 0 ? BLSW_COMPACT_TILE : part == 1 ? BLSW_COMPACT_INST : BLSW_COMPACT_PAIR, e, lane)));
+        uint32_t borrow = 0;
+#pragma unroll
+        for (int l = 0; l < 12; l++) subb32(z.l[l], P[l], borrow);
+        if (!borrow) atomicMin(out + i, (unsigned long long)base + k);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------- host side
 int hip_ok(hipError_t e, const char* what) {
     if (e != hipSuccess) {
@@ -216,6 +333,16 @@ struct blsw_r1cs {
     Enc enc;
     std::vector<uint64_t> blk;  // host copy of the block starts (a row range -> blocks)
     std::vector<uint32_t> head;  // head_cover (r1cs_encode.hpp): the head rows of any head_len without the CSR
+    uint64_t nnz[3];
+    // pair_families of every multi layout a call has named (blsw_r1cs_handle_pair_families): computed once from the encoding on the device, keyed by
+    // what the detector reads — K, the runs and the strides, not the step size (family_key). The only state of the handle a check changes: behind
+    // families_lock, and an entry never moves once it is made (the calls keep a pointer to its vector).
+    struct Families {
+        blsw_compact_layout_multi_t key;
+        std::vector<PairFamily> fam;
+    };
+    std::vector<std::unique_ptr<Families>> families;
+    std::mutex families_lock;
 };
 
 int blsw_r1cs_device_bytes(const blsw_matrices_info_t* info, const blsw_matrices_t* m, uint64_t* bytes) {
@@ -266,6 +393,7 @@ int blsw_r1cs_create(blsw_r1cs_t** out, const blsw_matrices_info_t* info, const 
     r->n_cons = info->n_constraints;
     r->n_inst = info->n_instance_vars;
     r->n_wit = info->n_witness;
+    for (int mi = 0; mi < 3; mi++) r->nnz[mi] = info->nnz[mi];
     for (int mi = 0; mi < 3; mi++) {
         r->enc.rp[mi] = reinterpret_cast<const uint64_t*>(base + e.off_rp[mi]);
         r->enc.ent[mi] = reinterpret_cast<const blsw_u2*>(base + e.off_ent[mi]);
@@ -550,5 +678,169 @@ int blsw_r1cs_evaluate_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     Guard guard(r->device);
     KeysetCompactArgs a = make_keyset_compact_args(r, rows_layout, d_compact, ks, d_instance, instance_stride);
+    return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
+}
+
+// ---- the N+1-pair product's compact form (blsw_compact_layout_multi_t): the general source, and one pair per lane over the pair families
+namespace {
+
+int multi_args(const blsw_r1cs* r, const blsw_compact_layout_multi_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride) {
+    if (!r || !c || !d_compact || (reinterpret_cast<uintptr_t>(d_compact) & 15) || !compact_layout_multi_ok(*c) || c->n_witness != r->n_wit) return BLSW_ERR_ARG;
+    if (r->n_inst > 1 && (!d_instance || instance_stride < r->n_inst)) return BLSW_ERR_ARG;
+    if (d_instance && instance_stride < r->n_inst) return BLSW_ERR_ARG;
+    return BLSW_OK;
+}
+MultiCompactArgs make_multi_args(const blsw_r1cs* r, const blsw_compact_layout_multi_t* c, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride) {
+    MultiCompactArgs a;
+    static_cast<Args&>(a) = make_args(r, d_instance, instance_stride, nullptr, 0, c->n, 0);
+    a.c = *c;
+    a.compact = reinterpret_cast<const char*>(d_compact);
+    return a;
+}
+// n <= 65535 instances: one launch; the lanes past n of the last group of 64 idle (n = 4 and 32 are legal step sizes)
+int launch(const MultiCompactArgs& a, bool eval, hipStream_t st) {
+    dim3 grid((a.n_blk + WAVES - 1) / WAVES, (unsigned)((a.n + 63) / 64));
+    if (eval)
+        hipLaunchKernelGGL((k_r1cs<true, MultiCompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_r1cs<false, MultiCompactArgs>), grid, dim3(64 * WAVES), 0, st, a);
+    return hip_ok(hipGetLastError(), "launch");
+}
+// whose a column is under a multi layout (r1cs_encode.hpp: pair_families)
+struct MultiOwner {
+    const blsw_compact_layout_multi_t& c;
+    uint32_t n_inst;
+    ColOwner operator()(uint32_t col) const {
+        if (col == 0) return {PAIR_CONST, 0};
+        if (col < n_inst) return {PAIR_SHARED, 0};
+        uint32_t j, row, bit;
+        const uint32_t region = compact_place_multi(c, col - n_inst, &j, &row, &bit);
+        if (region == BLSW_COMPACT_BIT) return {(int32_t)j, c.stride_hash};
+        if (region != BLSW_COMPACT_TILE) return {PAIR_SHARED, 0};
+        for (int r = 0; r < 6; r++)
+            if (row >= c.pair_run_row[r] && row - c.pair_run_row[r] < c.pair_run_len[r]) return {(int32_t)j, c.pair_run_stride[r]};
+        return {PAIR_SHARED, 0};
+    }
+};
+// the families of the handle's matrices under *c: kept per layout; the first call reads row pointers and entries back from the device
+// the layout without what depends on the step size: the families are a function of the rest (pair_families reads K, the runs and the strides)
+blsw_compact_layout_multi_t family_key(const blsw_compact_layout_multi_t& c) {
+    blsw_compact_layout_multi_t k = c;
+    k.n = k.off_staging = k.off_inst = k.off_pair = k.total = 0;
+    k.inst_tile_w = 0;
+    return k;
+}
+int handle_families(blsw_r1cs* r, const blsw_compact_layout_multi_t* c, const std::vector<PairFamily>** out) {
+    const blsw_compact_layout_multi_t key = family_key(*c);
+    std::lock_guard<std::mutex> lock(r->families_lock);
+    for (const auto& f : r->families)
+        if (memcmp(&f->key, &key, sizeof(key)) == 0) {
+            *out = &f->fam;
+            return BLSW_OK;
+        }
+    std::vector<uint64_t> rp[3];
+    std::vector<blsw_u2> ent[3];
+    const uint64_t* rpp[3];
+    const blsw_u2* entp[3];
+    for (int mi = 0; mi < 3; mi++) {
+        rp[mi].resize(r->n_cons + 1);
+        ent[mi].resize(r->nnz[mi]);
+        if (hip_ok(hipMemcpy(rp[mi].data(), r->enc.rp[mi], (r->n_cons + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy")) return BLSW_ERR_HIP;
+        if (r->nnz[mi] && hip_ok(hipMemcpy(ent[mi].data(), r->enc.ent[mi], r->nnz[mi] * sizeof(blsw_u2), hipMemcpyDeviceToHost), "hipMemcpy")) return BLSW_ERR_HIP;
+        rpp[mi] = rp[mi].data();
+        entp[mi] = ent[mi].data();
+    }
+    r->families.emplace_back(new blsw_r1cs::Families{key, pair_families(r->n_cons, rpp, entp, c->n_pairs, MultiOwner{*c, (uint32_t)r->n_inst})});
+    *out = &r->families.back()->fam;
+    return BLSW_OK;
+}
+int families_out(const std::vector<PairFamily>& fam, uint64_t capacity, uint64_t* first_row, uint64_t* rows_per_pair, uint64_t* count) {
+    if (capacity && (!first_row || !rows_per_pair)) return BLSW_ERR_ARG;
+    for (uint64_t f = 0; f < fam.size() && f < capacity; f++) first_row[f] = fam[f].first, rows_per_pair[f] = fam[f].rows;
+    *count = fam.size();
+    return BLSW_OK;
+}
+
+}  // namespace
+
+int blsw_r1cs_pair_families(const blsw_matrices_info_t* info, const blsw_matrices_t* m, const blsw_compact_layout_multi_t* layout, uint64_t capacity, uint64_t* first_row,
+                            uint64_t* rows_per_pair, uint64_t* count) {
+    if (!count || !layout || !compact_layout_multi_ok(*layout)) return BLSW_ERR_ARG;
+    Encoded e;
+    const int rc = encode(info, m, &e);
+    if (rc) return rc;
+    if (layout->n_witness != info->n_witness) return BLSW_ERR_ARG;
+    const uint64_t* rp[3] = {m->row_ptr[0], m->row_ptr[1], m->row_ptr[2]};
+    const blsw_u2* ent[3] = {e.ent[0].data(), e.ent[1].data(), e.ent[2].data()};
+    return families_out(pair_families(info->n_constraints, rp, ent, layout->n_pairs, MultiOwner{*layout, (uint32_t)info->n_instance_vars}), capacity, first_row, rows_per_pair, count);
+}
+
+int blsw_r1cs_handle_pair_families(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, uint64_t capacity, uint64_t* first_row, uint64_t* rows_per_pair, uint64_t* count) {
+    if (!r || !count || !layout || !compact_layout_multi_ok(*layout) || layout->n_witness != r->n_wit) return BLSW_ERR_ARG;
+    Guard guard(r->device);
+    const std::vector<PairFamily>* fam = nullptr;
+    if (int rc = handle_families(r, layout, &fam)) return rc;
+    return families_out(*fam, capacity, first_row, rows_per_pair, count);
+}
+
+int blsw_r1cs_check_compact_multi_ex(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                                     uint32_t use_families, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    if (multi_args(r, layout, d_compact, d_instance, instance_stride) || !d_first_unsatisfied || use_families > 1) return BLSW_ERR_ARG;
+    static constexpr uint32_t R2[12] = BLSW_R2_LIMBS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    static const std::vector<PairFamily> none;
+    const std::vector<PairFamily>* fam = &none;
+    if (use_families)
+        if (int rc = handle_families(r, layout, &fam)) return rc;
+    const uint64_t n = layout->n, K = layout->n_pairs;
+    MultiCompactArgs a = make_multi_args(r, layout, d_compact, d_instance, instance_stride);
+    a.k = fp_const(R2);
+    a.bad = reinterpret_cast<uint64_t*>(d_first_unsatisfied);
+    if (hip_ok(hipMemsetAsync(d_first_unsatisfied, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;  // all ones = -1 = satisfied
+    // the rows in front of, between and behind the families: one instance per lane; a family: its template block, one pair per lane. Every launch
+    // lowers bad[i] by atomicMin, so their order does not matter. At most 2 * families + 1 launches.
+    uint64_t cursor = 0;
+    auto general = [&](uint64_t lo, uint64_t hi) {
+        if (lo >= hi) return (int)BLSW_OK;
+        set_rows(r, a, lo, hi);
+        return launch(a, false, st);
+    };
+    for (const PairFamily& f : *fam) {
+        if (int rc = general(cursor, f.first)) return rc;
+        PairArgs pa;
+        static_cast<MultiCompactArgs&>(pa) = a;
+        pa.fam_rows = f.rows;
+        set_rows(r, pa, f.first, f.first + f.rows);
+        hipLaunchKernelGGL(k_r1cs_pairs, dim3((pa.n_blk + WAVES - 1) / WAVES, (unsigned)(n * K / 64)), dim3(64 * WAVES), 0, st, pa);
+        if (hip_ok(hipGetLastError(), "launch")) return BLSW_ERR_HIP;
+        cursor = f.first + K * f.rows;
+    }
+    if (int rc = general(cursor, r->n_cons)) return rc;
+    if (!d_first_unreduced) return BLSW_OK;
+    // the instance vectors (the plain pass over the first n_inst indices of z), then the staged elements of the three row regions
+    if (hip_ok(hipMemsetAsync(d_first_unreduced, 0xFF, n * 8, st), "hipMemsetAsync")) return BLSW_ERR_HIP;
+    unsigned long long* unr = reinterpret_cast<unsigned long long*>(d_first_unreduced);
+    if (d_instance)
+        hipLaunchKernelGGL(k_r1cs_unreduced, dim3(1, (unsigned)n), dim3(256), 0, st, d_instance, instance_stride, nullptr, 0, (uint32_t)r->n_inst, r->n_inst, unr);
+    auto chunks = [](uint32_t rows, uint32_t per) { return std::min<uint32_t>((rows + per - 1) / per, 256); };
+    const uint32_t base = (uint32_t)r->n_inst;
+    if (layout->rows_p) hipLaunchKernelGGL(k_r1cs_unreduced_multi, dim3(chunks(layout->rows_p, 4), (unsigned)(n * K / 64)), dim3(256), 0, st, *layout, a.compact, base, 0u, unr);
+    if (layout->rows_i) hipLaunchKernelGGL(k_r1cs_unreduced_multi, dim3(chunks(layout->rows_i, 4), (unsigned)((n + 63) / 64)), dim3(256), 0, st, *layout, a.compact, base, 1u, unr);
+    if (layout->pair_rows) hipLaunchKernelGGL(k_r1cs_unreduced_multi, dim3(chunks(layout->pair_rows, 256), (unsigned)n), dim3(256), 0, st, *layout, a.compact, base, 2u, unr);
+    return hip_ok(hipGetLastError(), "launch");
+}
+
+int blsw_r1cs_check_compact_multi(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                                  int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream) {
+    return blsw_r1cs_check_compact_multi_ex(r, layout, d_compact, d_instance, instance_stride, 1, d_first_unsatisfied, d_first_unreduced, stream);
+}
+
+int blsw_r1cs_evaluate_compact_multi(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance, uint64_t instance_stride,
+                                     uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream) {
+    if (multi_args(r, layout, d_compact, d_instance, instance_stride) || !d_az || !d_bz || !d_cz || !row_window_ok(r, row_begin, row_count)) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Guard guard(r->device);
+    MultiCompactArgs a = make_multi_args(r, layout, d_compact, d_instance, instance_stride);
     return run_evaluate(r, a, row_begin, row_count, d_az, d_bz, d_cz, st);
 }

@@ -315,6 +315,155 @@ BLSW_HD uint32_t compact_locate(const blsw_compact_layout_t& c, uint32_t k, uint
     *byte_offset = c.off_pair + (lane * c.pair_rows + (row - c.split_row)) * sizeof(Fp);
     return BLSW_COMPACT_PAIR;
 }
+// blsw_compact_layout_multi_t (include/blsw.h) of the steps of n instances of an N+1-pair engine: what compact_form(n, w, K) and launch_place_multi know
+inline blsw_compact_layout_multi_t compact_layout_multi(uint64_t n, const blsw_layout_t& L) {
+    const uint32_t K = L.n_pairs;
+    const Workspace w = carve(nullptr, n * K, L, true, DEFAULT_MODES, n);
+    const CompactForm cf = compact_form(n, w, K);
+    const blsw_layout_t S = staging_layout_multi(L).LS;
+    blsw_compact_layout_multi_t c;
+    memset(&c, 0, sizeof(c));
+    c.n = n;
+    c.off_staging = cf.off_staging;
+    c.off_inst = cf.off_inst;
+    c.off_pair = cf.off_pair;
+    c.total = cf.total;
+    c.n_pairs = K;
+    c.n_witness = L.n_witness;
+    c.sha_bits = L.sha_bits;
+    c.sha_words = (uint32_t)w.sha_words;
+    c.off_expand = L.off_expand;
+    c.stride_hash = L.stride_hash;
+    c.rows_p = w.rows_p;
+    c.rows_i = w.rows_i;
+    c.pair_rows = w.pair_rows;
+    c.inst_tile_w = cf.inst_tile_w;
+    c.off_miller = L.off_miller;
+    const uint32_t src[7] = {S.off_msg, S.off_pk_alloc, S.off_pk_not_zero, S.off_map0, S.off_prep_h, S.off_prep_pk, w.rows_p};  // launch_place_multi's runs
+    const uint32_t dst[6] = {L.off_msg, L.off_pk_alloc, L.off_pk_not_zero, L.off_map0, L.off_prep_h, L.off_prep_pk};
+    const uint32_t str[6] = {L.stride_msg, L.stride_pk_alloc, L.stride_pk_not_zero, L.stride_hash, L.stride_prep_h, L.stride_prep_pk};
+    for (int r = 0; r < 6; r++) c.pair_run_row[r] = src[r], c.pair_run_off[r] = dst[r], c.pair_run_stride[r] = str[r], c.pair_run_len[r] = src[r + 1] - src[r];
+    c.inst_run_row[0] = S.off_sig_alloc;
+    c.inst_run_row[1] = S.off_prep_sig;
+    c.inst_run_off[0] = L.off_sig_alloc;
+    c.inst_run_off[1] = L.off_prep_sig;
+    c.inst_run_len[0] = S.off_prep_sig - S.off_sig_alloc;
+    c.inst_run_len[1] = w.rows_i - S.off_prep_sig;
+    return c;
+}
+#define BLSW_COMPACT_NONE 0xffffffffu  // compact_place_multi: no region holds the witness (never for a struct compact_layout_multi_ok accepts)
+// Where witness k of an N+1-pair instance lives, the part that does not depend on the instance: the region, the pair j whose lane holds it (BIT,
+// TILE; 0 otherwise) and the row — the u32 word of the lane's bit stream (BIT, *bit = the position in it) or the staged row of the region. The
+// inverse of k_place_runs / k_place_rows and of the expansion's off_expand + j * stride_hash + b rule. k is wave-uniform in the checker: all of
+// this is scalar arithmetic.
+BLSW_HD uint32_t compact_place_multi(const blsw_compact_layout_multi_t& c, uint32_t k, uint32_t* j, uint32_t* row, uint32_t* bit) {
+    *j = 0;
+    *row = 0;
+    *bit = 0;
+    if (k >= c.off_miller) {
+        *row = k - c.off_miller;
+        return *row < c.pair_rows ? (uint32_t)BLSW_COMPACT_PAIR : BLSW_COMPACT_NONE;
+    }
+    if (k >= c.off_expand && c.stride_hash) {
+        const uint32_t d = k - c.off_expand, jj = d / c.stride_hash, b = d - jj * c.stride_hash;
+        if (jj < c.n_pairs) {  // pair jj's hash_to_g2: its SHA bits, then run 3 (compact_layout_multi_ok: pair_run_len[3] = stride_hash - sha_bits) — most of z
+            *j = jj;
+            if (b < c.sha_bits) {
+                *row = b >> 5;
+                *bit = b & 31;
+                return BLSW_COMPACT_BIT;
+            }
+            *row = c.pair_run_row[3] + (b - c.sha_bits);
+            return BLSW_COMPACT_TILE;
+        }
+    }
+    for (int r = 0; r < 6; r++) {
+        if (r == 3 || !c.pair_run_len[r] || !c.pair_run_stride[r] || k < c.pair_run_off[r]) continue;
+        const uint32_t d = k - c.pair_run_off[r], jj = d / c.pair_run_stride[r], t = d - jj * c.pair_run_stride[r];
+        if (jj < c.n_pairs && t < c.pair_run_len[r]) {
+            *j = jj;
+            *row = c.pair_run_row[r] + t;
+            return BLSW_COMPACT_TILE;
+        }
+    }
+    for (int r = 0; r < 2; r++)
+        if (k >= c.inst_run_off[r] && k - c.inst_run_off[r] < c.inst_run_len[r]) {
+            *row = c.inst_run_row[r] + (k - c.inst_run_off[r]);
+            return BLSW_COMPACT_INST;
+        }
+    return BLSW_COMPACT_NONE;
+}
+// ... and the part that does: the byte offset of (region, row) for a lane — the PAIR LANE i K + j for BIT and TILE, the instance for INST and PAIR
+BLSW_HD uint64_t compact_address_multi(const blsw_compact_layout_multi_t& c, uint32_t region, uint32_t row, uint64_t lane) {
+    const uint64_t tile = lane >> 6, l = lane & 63;
+    if (region == BLSW_COMPACT_BIT)
+        return (tile * bits_tile_words(c.sha_words) + (uint64_t)(row / BLSW_BITS_CHUNK_WORDS) * (64 * BLSW_BITS_CHUNK_WORDS) + l * BLSW_BITS_CHUNK_WORDS +
+                row % BLSW_BITS_CHUNK_WORDS) * 4;
+    if (region == BLSW_COMPACT_TILE) return c.off_staging + ((tile * c.rows_p + row) * 64 + l) * sizeof(Fp);
+    if (region == BLSW_COMPACT_INST) return c.off_inst + (((lane / c.inst_tile_w) * c.rows_i + row) * c.inst_tile_w + lane % c.inst_tile_w) * sizeof(Fp);
+    return c.off_pair + (lane * c.pair_rows + row) * sizeof(Fp);
+}
+// witness k of instance i: the two together (blsw_compact_locate_multi; the general path of the device checker)
+BLSW_HD uint32_t compact_locate_multi(const blsw_compact_layout_multi_t& c, uint32_t k, uint64_t i, uint64_t* byte_offset, uint32_t* bit) {
+    uint32_t j, row;
+    const uint32_t region = compact_place_multi(c, k, &j, &row, bit);
+    *byte_offset = 0;
+    if (region == BLSW_COMPACT_NONE) return region;
+    *byte_offset = compact_address_multi(c, region, row, region <= BLSW_COMPACT_TILE ? i * c.n_pairs + j : i);
+    return region;
+}
+// The struct is exactly what compact_layout_multi gives for some shape: then the runs tile [0, n_witness) (every k has one place) and every address
+// compact_address_multi derives for k < n_witness, instance < n lies inside its region, the regions inside [0, total). Checked on the host before
+// the locator or a kernel reads through a caller's struct.
+inline bool compact_layout_multi_ok(const blsw_compact_layout_multi_t& c) {
+    const uint32_t K = c.n_pairs;
+    // n is the caller's u64: bounded on its own before any product is formed (n K <= 65535 is the engine's rule)
+    if (c.n == 0 || K < 2 || K > 4096 || c.n > 65535 / K || !compact_shape_ok(c.n, K) || c.reserved) return false;
+    if (c.inst_tile_w != (c.n % 64 == 0 ? 64u : (uint32_t)c.n)) return false;
+    if (c.sha_bits > c.stride_hash || c.sha_words != align_up((c.sha_bits + 31) / 32 + 1, BLSW_BITS_CHUNK_WORDS)) return false;
+    if (c.off_miller > c.n_witness || c.pair_rows != c.n_witness - c.off_miller) return false;
+    // staged rows: the runs one after the other from row 0, a pair's copy of a run one stride after the previous pair's
+    uint32_t row = 0;
+    for (int r = 0; r < 6; r++) {
+        if (c.pair_run_row[r] != row || c.pair_run_len[r] > c.rows_p - row) return false;
+        if (r == 3 ? (c.pair_run_stride[r] != c.stride_hash || c.pair_run_len[r] != c.stride_hash - c.sha_bits || c.pair_run_off[r] - c.sha_bits != c.off_expand)
+                   : (c.pair_run_len[r] != c.pair_run_stride[r]))
+            return false;
+        row += c.pair_run_len[r];
+    }
+    if (row != c.rows_p) return false;
+    row = 0;
+    for (int r = 0; r < 2; r++) {
+        if (c.inst_run_row[r] != row || c.inst_run_len[r] > c.rows_i - row) return false;
+        row += c.inst_run_len[r];
+    }
+    if (row != c.rows_i) return false;
+    // the witness vector: the nine blocks (K copies of a run; the hash block with its bits; the instance runs; the instance rows), sorted, tile it
+    uint64_t lo[9], len[9];
+    for (int r = 0; r < 6; r++) lo[r] = r == 3 ? c.off_expand : c.pair_run_off[r], len[r] = (uint64_t)K * c.pair_run_stride[r];
+    for (int r = 0; r < 2; r++) lo[6 + r] = c.inst_run_off[r], len[6 + r] = c.inst_run_len[r];
+    lo[8] = c.off_miller;
+    len[8] = c.pair_rows;
+    uint64_t at = 0;
+    for (int done = 0; done < 9; done++) {  // the empty blocks first, then the one that starts where the last one ended
+        int pick = -1;
+        for (int b = 0; b < 9 && pick < 0; b++)
+            if (len[b] == 0 && lo[b] != ~0ull) pick = b;
+        for (int b = 0; b < 9 && pick < 0; b++)
+            if (len[b] && lo[b] == at) pick = b;
+        if (pick < 0) return false;
+        at += len[pick];
+        lo[pick] = ~0ull;
+        len[pick] = 1;
+    }
+    if (at != c.n_witness) return false;
+    // the buffer: compact_form's offsets
+    const uint64_t bits = bits_tile_words(c.sha_words) * (c.n * K / 64) * 4;
+    if (c.off_staging != align_up(bits, 256)) return false;
+    if (c.off_inst != align_up(c.off_staging + (uint64_t)c.rows_p * c.n * K * sizeof(Fp), 256)) return false;
+    if (c.off_pair != align_up(c.off_inst + (uint64_t)c.rows_i * c.n * sizeof(Fp), 256)) return false;
+    return c.total == align_up(c.off_pair + (uint64_t)c.pair_rows * c.n * sizeof(Fp), 256);
+}
 // a group of `steps` batches of n instances each, processed by one set of launches (N = steps * n * K lanes per chain;
 // K = (pk, msg) pairs per instance: 1 except for the N+1-pair product)
 struct Group {

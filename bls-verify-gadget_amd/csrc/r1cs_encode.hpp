@@ -161,5 +161,72 @@ inline uint64_t head_rows(const std::vector<uint32_t>& cover, uint64_t head_len)
     return lo;
 }
 
+
+// Pair families (blsw_r1cs_pair_families, blsw_r1cs_check_compact_multi): K consecutive blocks of R rows in which block j reads nothing but column 0
+// and witnesses of pair j, and equals block 0 with every witness column moved by j strides of its run and the same coefficient codes (encode() gives
+// equal coefficients equal codes). owner(column) says whose a column is: pair >= 0 a pair-local witness of that pair (stride: its run's), PAIR_CONST
+// column 0, PAIR_SHARED anything else (a public input, a witness of the instance). Nothing is assumed of the matrices: a candidate — the rows of
+// pair 0 up to the first row of pair 1 — becomes a family only when every entry of all K blocks has been compared. Of an encoding encode() made.
+struct PairFamily {
+    uint64_t first, rows;  // the template block [first, first + rows); block j follows at first + j * rows
+};
+struct ColOwner {
+    int32_t pair;
+    uint32_t stride;
+};
+constexpr int32_t PAIR_CONST = -1, PAIR_SHARED = -2;
+template <class Owner>
+inline std::vector<PairFamily> pair_families(uint64_t n_cons, const uint64_t* const rp[3], const blsw_u2* const ent[3], uint32_t K, Owner owner) {
+    std::vector<int32_t> own(n_cons);
+    for (uint64_t r = 0; r < n_cons; r++) {
+        int32_t o = PAIR_CONST;
+        for (int mi = 0; mi < 3 && o != PAIR_SHARED; mi++)
+            for (uint64_t k = rp[mi][r]; k < rp[mi][r + 1]; k++) {
+                const int32_t p = owner(ent[mi][k].x).pair;
+                if (p == PAIR_CONST) continue;
+                if (p == PAIR_SHARED || (o >= 0 && o != p)) {
+                    o = PAIR_SHARED;
+                    break;
+                }
+                o = p;
+            }
+        own[r] = o;
+    }
+    auto block_equal = [&](uint64_t r0, uint64_t rj, uint32_t j) {  // row rj == row r0 translated to pair j
+        for (int mi = 0; mi < 3; mi++) {
+            const uint64_t a0 = rp[mi][r0], a1 = rp[mi][r0 + 1], b0 = rp[mi][rj];
+            if (rp[mi][rj + 1] - b0 != a1 - a0) return false;
+            for (uint64_t k = 0; k < a1 - a0; k++) {
+                const blsw_u2 a = ent[mi][a0 + k], b = ent[mi][b0 + k];
+                const ColOwner o = owner(a.x);
+                const uint64_t want = o.pair == PAIR_CONST ? a.x : (uint64_t)a.x + (uint64_t)j * o.stride;
+                if (a.y != b.y || b.x != want) return false;
+            }
+        }
+        return true;
+    };
+    std::vector<PairFamily> fam;
+    uint64_t r = 0;
+    while (r < n_cons) {
+        if (own[r] != 0) {
+            r++;
+            continue;
+        }
+        uint64_t e = r;
+        while (e < n_cons && (own[e] == 0 || own[e] == PAIR_CONST)) e++;
+        const uint64_t R = e - r;
+        bool ok = K > 1 && e < n_cons && own[e] == 1 && R <= (n_cons - r) / K;
+        for (uint32_t j = 1; j < K && ok; j++)
+            for (uint64_t t = 0; t < R && ok; t++) ok = block_equal(r + t, r + (uint64_t)j * R + t, j);
+        if (ok) {
+            fam.push_back(PairFamily{r, R});
+            r += (uint64_t)K * R;
+        } else {
+            r = e;
+        }
+    }
+    return fam;
+}
+
 }  // namespace r1cs
 }  // namespace blsw

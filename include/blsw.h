@@ -378,7 +378,7 @@ int blsw_engine_expand_compact(blsw_engine_t* e, const void* d_compact, uint64_t
  *   pair rows   [n][pair_rows] elements at off_pair: staged row split_row + r of a lane (the pairing segments, instance-major)
  * Staged rows are the witness vector with the SHA segment cut out (staging_rows = n_witness - sha_bits); with options.g2_mode 1 the moved_len
  * witnesses from moved_lo on are staged last, from row moved_at on (moved_len 0 otherwise). Elements are always Montgomery form.
- * The N+1-pair product's compact form (pair tiles and instance tiles) is not described by this struct. */
+ * The N+1-pair product's compact form (pair tiles and instance tiles) is described by blsw_compact_layout_multi_t below, not by this struct. */
 typedef struct {
     uint64_t n, off_staging, off_pair, total; /* instances of the step; byte offsets of the two row regions; bytes of the step */
     uint32_t n_witness, off_expand, sha_bits, sha_words, split_row, staging_rows, pair_rows, moved_lo, moved_len, moved_at;
@@ -557,6 +557,71 @@ int blsw_r1cs_check_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* 
                                    const uint64_t* d_instance, uint64_t instance_stride, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
 int blsw_r1cs_evaluate_compact_keyset(blsw_r1cs_t* r, const blsw_compact_layout_t* rows_layout, const void* d_compact, const blsw_keyset_t* ks, const uint64_t* d_instance,
                                       uint64_t instance_stride, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz, void* stream);
+/* The N+1-pair product's compact form, described, and a step checked straight from it (new symbols; the ABI number is unchanged).
+ * A compact step of n instances of K = n_pairs pairs (n K a multiple of 64, n a divisor or a multiple of 64) is four regions back to back; pair j of
+ * instance i is PAIR LANE p = i K + j, lane p & 63 of pair tile p / 64:
+ *   bit words       [n K / 64][sha_words/16][64][16] u32 at offset 0: witness off_expand + j stride_hash + b (b < sha_bits) is bit b & 31 of word b / 32
+ *                   of pair lane p's stream
+ *   pair tiles      [n K / 64][rows_p][64] elements at off_staging: staged row e < rows_p of a pair lane. Row e of run r (pair_run_row[r] <= e <
+ *                   pair_run_row[r] + pair_run_len[r]) is witness pair_run_off[r] + j pair_run_stride[r] + (e - pair_run_row[r]). The six runs, in row
+ *                   order: message, key allocation, pk != 0, hash_to_g2 behind its SHA bits, prepare(H), prepare(pk); a run may be empty (len 0)
+ *   instance tiles  [ceil(n / 64)][rows_i][inst_tile_w] elements at off_inst, inst_tile_w = 64 or n (a step that is a part of one tile): staged row e of
+ *                   instance lane i, at lane i % inst_tile_w of tile i / inst_tile_w. The two runs: signature allocation, prepare(sig) (inst_run_*)
+ *   instance rows   [n][pair_rows] elements at off_pair: witness off_miller + r of instance i (Miller loop, final exponentiation, is_one)
+ * Elements are always Montgomery form. */
+typedef struct {
+    uint64_t n, off_staging, off_inst, off_pair, total; /* instances of the step; byte offsets of the three row regions; bytes of the step */
+    uint32_t n_pairs, n_witness, sha_bits, sha_words, off_expand, stride_hash, rows_p, rows_i, pair_rows, inst_tile_w, off_miller, reserved;
+    uint32_t pair_run_row[6], pair_run_off[6], pair_run_stride[6], pair_run_len[6];
+    uint32_t inst_run_row[2], inst_run_off[2], inst_run_len[2];
+} blsw_compact_layout_multi_t;
+#define BLSW_COMPACT_INST 3 /* the fourth region blsw_compact_locate_multi reports: an instance tile (BLSW_COMPACT_TILE: a pair tile; _PAIR: the instance rows) */
+/* The layout of the compact steps of an engine created with blsw_engine_create_multi_inputs(n, msg_len, .., options, multi_inputs, ..) — any staged
+ * engine. total == blsw_engine_compact_bytes of such an engine. BLSW_ERR_ARG: a NULL pointer, options.n_pairs < 2, a shape that cannot leave in compact
+ * form (n K % 64 != 0, or n neither a divisor nor a multiple of 64), and every option or mask set blsw_engine_create_multi_inputs refuses for a staged
+ * engine. blsw_compact_layout keeps refusing n_pairs > 1. Host only. */
+int blsw_compact_layout_multi(uint64_t n, uint32_t msg_len, const blsw_engine_options_t* options, uint32_t multi_inputs, blsw_compact_layout_multi_t* out);
+/* witness k (< n_witness) of instance `instance` (< n): *region = BLSW_COMPACT_BIT / _TILE / _INST / _PAIR, *byte_offset and *bit as blsw_compact_locate.
+ * The inverse of the placement of the four regions; the one statement of the rule: the device checker evaluates the same function.
+ * BLSW_ERR_ARG: a NULL pointer, k or instance out of range, a struct that is not exactly what blsw_compact_layout_multi gives for some engine shape:
+ * n is bounded on its own (n <= 65535 / n_pairs) before any product with it is formed, so no 64-bit product wraps, and every derived address is
+ * proved inside [0, total) before it is used. Host only. */
+int blsw_compact_locate_multi(const blsw_compact_layout_multi_t* layout, uint32_t k, uint64_t instance, uint32_t* region, uint64_t* byte_offset, uint32_t* bit);
+/* blsw_compact_locate_multi of witnesses [k_begin, k_begin + count) of one instance: regions [count] u8, byte_offsets [count] u64, bits [count] u8. Host only. */
+int blsw_compact_locate_multi_range(const blsw_compact_layout_multi_t* layout, uint32_t k_begin, uint32_t count, uint64_t instance, uint8_t* regions,
+                                    uint64_t* byte_offsets, uint8_t* bits);
+/* Pair families of a constraint system under such a layout: runs of K consecutive blocks of R rows in which block j reads nothing but column 0 and
+ * witnesses of pair j (bit words and pair tiles) and equals block 0 entry for entry, every witness column moved by j strides of its run and every
+ * coefficient identical. The checker evaluates ONE template block per family with one pair per lane. Nothing is assumed of the matrices: every entry
+ * of every block is compared, and a system without such blocks has no family (the check then reads every row through the general path).
+ * first_row / rows_per_pair [capacity] (may be NULL with capacity 0) receive the families in row order; *count = their number, also when it exceeds
+ * capacity. BLSW_ERR_ARG: a NULL pointer, a CSR blsw_r1cs_create refuses, an inconsistent layout, layout->n_witness != info->n_witness.
+ * Host only. blsw_r1cs_handle_pair_families answers the same for the matrices a handle was created from. The handle keeps no CSR: the first call
+ * for a given K, set of runs and strides (the step size n does not enter) copies row pointers and entries back from the device with blocking
+ * hipMemcpy calls — it synchronises the device, must not be made while a stream capture is in progress, and takes host time (1 s at K = 16) —
+ * and the result stays on the handle; call it once before capturing or timing checks. This cache is the only state of a handle that a check,
+ * an evaluation or this call changes; it is guarded by a mutex, so calls on one handle from several threads remain safe. */
+int blsw_r1cs_pair_families(const blsw_matrices_info_t* info, const blsw_matrices_t* m, const blsw_compact_layout_multi_t* layout, uint64_t capacity,
+                            uint64_t* first_row, uint64_t* rows_per_pair, uint64_t* count);
+int blsw_r1cs_handle_pair_families(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, uint64_t capacity, uint64_t* first_row, uint64_t* rows_per_pair,
+                                   uint64_t* count);
+/* blsw_r1cs_check_compact / _evaluate_compact for a step of the N+1-pair product: n = layout->n instances (any legal step size, 4 and 32 included),
+ * outputs [n], rows numbered as in the matrix, Montgomery form, d_instance as there. The check evaluates every pair family with one pair per lane
+ * (whole tile rows, the template's entries read once instead of K times) and every other row with one instance per lane; the evaluation takes the
+ * general path for any row window. d_first_unreduced: the instance vector, then every staged element of the three row regions at its index of z.
+ * blsw_r1cs_check_compact_multi_ex is the same call with one more argument and is a public, supported symbol: use_families 1 is
+ * blsw_r1cs_check_compact_multi; use_families 0 sends every row through the general path (same results; it needs no families and therefore never
+ * reads the encoding back: the route for a caller inside a stream capture who has not called blsw_r1cs_handle_pair_families first, and the
+ * yardstick of tools/r1cs_rate.py --multi); a value above 1 is BLSW_ERR_ARG. The first check with families per (handle, K, runs) computes them
+ * as blsw_r1cs_handle_pair_families does, with its blocking copies. BLSW_ERR_ARG before any launch, nothing written: the rules
+ * of blsw_r1cs_check_compact with the layout rules of blsw_compact_locate_multi. */
+int blsw_r1cs_check_compact_multi(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance,
+                                  uint64_t instance_stride, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+int blsw_r1cs_check_compact_multi_ex(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance,
+                                     uint64_t instance_stride, uint32_t use_families, int64_t* d_first_unsatisfied, int64_t* d_first_unreduced, void* stream);
+int blsw_r1cs_evaluate_compact_multi(blsw_r1cs_t* r, const blsw_compact_layout_multi_t* layout, const void* d_compact, const uint64_t* d_instance,
+                                     uint64_t instance_stride, uint64_t row_begin, uint64_t row_count, uint64_t* d_az, uint64_t* d_bz, uint64_t* d_cz,
+                                     void* stream);
 
 /* Input decode (PublicKey::try_from / Signature::try_from -> deserialize_compressed, src/bls.rs:219-242, 316-339):
  *   d_pk48 [n][48], d_sig96 [n][96]  ZCash-format compressed points

@@ -238,6 +238,34 @@ class ConstraintSystem {
         d_bad.download(bad.data(), layout.n * 8);
         return bad;
     }
+    // The same for a step of the N+1-pair product (blsw_r1cs_check_compact_multi): `layout` is blsw_compact_layout_multi's, of the engine that produced
+    // the step with blsw_engine_submit_multi_compact. Every pair family of the system is evaluated with one pair per lane, the other rows with one
+    // instance per lane; the first call per layout finds the families (pair_families below).
+    std::vector<int64_t> which_is_unsatisfied(const blsw_compact_layout_multi_t& layout, const void* d_compact, const uint64_t* d_instance = nullptr) {
+        if (!r1cs_) build_checker();
+        if (layout_.n_instance_vars > 1 && !d_instance) {
+            if (!instance_.get() || layout.n != n_) throw Error("which_is_unsatisfied(compact multi): instance vectors of layout.n systems", BLSW_ERR_ARG);
+            d_instance = static_cast<const uint64_t*>(instance_.get());
+        }
+        detail::DeviceBytes d_bad(layout.n * 8);
+        check(blsw_r1cs_check_compact_multi(r1cs_, &layout, d_compact, d_instance, d_instance ? layout_.n_instance_vars : 0, static_cast<int64_t*>(d_bad.get()), nullptr,
+                                            nullptr),
+              "blsw_r1cs_check_compact_multi");
+        std::vector<int64_t> bad(layout.n);
+        d_bad.download(bad.data(), layout.n * 8);
+        return bad;
+    }
+    // {first row, rows per pair} of every pair family of this system under `layout` (blsw_r1cs_handle_pair_families)
+    std::vector<std::pair<uint64_t, uint64_t>> pair_families(const blsw_compact_layout_multi_t& layout) {
+        if (!r1cs_) build_checker();
+        uint64_t count = 0;
+        check(blsw_r1cs_handle_pair_families(r1cs_, &layout, 0, nullptr, nullptr, &count), "blsw_r1cs_handle_pair_families");
+        std::vector<uint64_t> first(count), rows(count);
+        check(blsw_r1cs_handle_pair_families(r1cs_, &layout, count, first.data(), rows.data(), &count), "blsw_r1cs_handle_pair_families");
+        std::vector<std::pair<uint64_t, uint64_t>> out;
+        for (uint64_t f = 0; f < count; f++) out.emplace_back(first[f], rows[f]);
+        return out;
+    }
     // The committee, once (blsw_r1cs_check_keyset): the first unsatisfied one of the rows that read nothing but the set's table, or -1; *first_unreduced
     // (optional): the index of z of the first table element >= p, or -1. The table in either element form.
     int64_t check(const KeySet& keys, int64_t* first_unreduced = nullptr) {

@@ -19,7 +19,8 @@ BEGIN, END = "<!-- BEGIN GENERATED RUST BINDING (tools/gen_bindings.py) -->", "<
 SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64", "int": "i32", "float": "f32", "double": "f64", "void": "c_void"}
 STRUCT_NAMES = {"blsw_layout_t": "BlswLayout", "blsw_engine_options_t": "BlswEngineOptions", "blsw_engine_t": "BlswEngine",
                 "blsw_matrices_t": "BlswMatrices", "blsw_matrices_info_t": "BlswMatricesInfo",
-                "blsw_r1cs_t": "BlswR1cs", "blsw_compact_layout_t": "BlswCompactLayout", "blsw_keyset_t": "BlswKeyset"}
+                "blsw_r1cs_t": "BlswR1cs", "blsw_compact_layout_t": "BlswCompactLayout", "blsw_compact_layout_multi_t": "BlswCompactLayoutMulti",
+                "blsw_keyset_t": "BlswKeyset"}
 
 
 def strip_comments(text):

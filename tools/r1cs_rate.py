@@ -24,7 +24,16 @@ the same steps (HIP-event time per call; median / min / max of --reps >= 5 calls
     check_keyset          (d) blsw_r1cs_check_keyset alone: the committee's head rows, once per set
 The yardstick of every leg is (a). Every GPU step runs under a time limit; when one expires or fails the process ends there and nothing follows.
 
-    python tools/r1cs_rate.py --keyset [--n 128] [--keys 512] [--reps 5] [--steps 2] [--limit 240]"""
+    python tools/r1cs_rate.py --keyset [--n 128] [--keys 512] [--reps 5] [--steps 2] [--limit 240]
+
+--multi: from a step of the N+1-pair product in compact wire form to a verdict, three routes interleaved call by call in one process over the same
+steps (HIP-event time per call; median / min / max of --reps >= 5 calls each after one warm-up round), one JSON line per step size:
+    expand_then_check     (a) blsw_engine_expand_compact into n witness vectors, then blsw_r1cs_check on them (the only route before this form was described)
+    check_compact         (b) blsw_r1cs_check_compact_multi: the pair families one pair per lane, the other rows one instance per lane
+    check_compact_general (c) the same call with the families switched off (blsw_r1cs_check_compact_multi_ex, use_families 0): every row one instance per lane
+The yardstick of (b) and (c) is (a). The steps are satisfied systems whose Boolean is false (keys, messages and signature do not belong together).
+
+    python tools/r1cs_rate.py --multi [--pairs 16] [--multi-n 4,64] [--reps 5] [--steps 2] [--limit 240]"""
 import argparse
 import importlib
 import json
@@ -212,6 +221,86 @@ def keyset_legs(a):
         sys.exit(1)
 
 
+def multi_legs(a):
+    """--multi: the routes from a compact step of the N+1-pair product to a verdict, alternating, over the same steps"""
+    import torch
+
+    from tools.agg_inputs_rate import StepLimit
+
+    pkg = importlib.import_module("bls-verify-gadget_amd")
+    workload = importlib.import_module("bls-verify-gadget_amd.workload")
+    dev = torch.device("cuda:0")
+    reps = max(5, a.reps)
+    K = a.pairs
+    t0 = time.time()
+    mats = pkg.matrices(32, n_pairs=K)
+    t_mats = time.time() - t0
+    nc = int(mats["n_constraints"])
+    with StepLimit(a.limit, "set-up"):
+        chk = pkg.ConstraintChecker.from_matrices(mats, dev)
+    ok = True
+    for n in [int(x) for x in a.multi_n.split(",")]:
+        with StepLimit(a.limit, "set-up of n = %d" % n):
+            pk, msg, sig, _ = workload.make_batch(pkg, n * K * a.steps, device=dev, tamper_every=0)
+            eng = pkg.WitnessEngine(n, 32, max_steps=2, n_buffers=2, device=dev, n_pairs=K)
+            lay = eng.compact_layout()
+            assert lay.total == eng.compact_bytes() and lay.n_witness == chk.n_witness
+            comp = eng.new_compact_buffer(a.steps)
+            for s in range(a.steps):
+                sl = slice(s * n * K, (s + 1) * n * K)
+                eng.submit_multi_compact(pk[sl].reshape(n, K, 12).contiguous(), msg[sl].reshape(n, K, 32).contiguous(), sig[s * n:(s + 1) * n].contiguous(), comp[s])
+            eng.flush()
+            torch.cuda.synchronize()
+            w = eng.new_witness_tensor()  # the receiver's n expanded vectors (leg a only)
+            t0 = time.time()
+            fam = chk.pair_families(lay)  # once per (handle, layout): not part of a timed call
+            t_fam = time.time() - t0
+
+        def leg_a(s):
+            eng.expand_compact(comp[s], w)
+            return chk.which_is_unsatisfied(w)
+
+        legs = {"expand_then_check": leg_a, "check_compact": lambda s: chk.which_is_unsatisfied_compact(lay, comp[s]),
+                "check_compact_general": lambda s: chk._check_compact(lay, comp[s], None, None, False, _use_families=False)[0]}
+        ms = {k: [] for k in legs}
+        same = True
+        for rep_i in range(reps + 1):  # the first repetition warms up
+            s = rep_i % a.steps
+            outs = {}
+            for k, fn in legs.items():  # alternating: a, b, c, a, ...
+                with StepLimit(a.limit, "repetition %d of %s" % (rep_i, k)):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    outs[k] = fn(s)
+                    e1.record()
+                    torch.cuda.synchronize()
+                if rep_i:
+                    ms[k].append(e0.elapsed_time(e1))
+            same = same and torch.equal(outs["expand_then_check"], outs["check_compact"]) and torch.equal(outs["check_compact"], outs["check_compact_general"])
+            same = same and bool((outs["check_compact"] < 0).all())
+        eng.close()
+        del w, comp
+        fam_rows = sum(R for _, R in fam) * K
+        entries = {name: np.diff(mats[name][0].astype(np.int64)) for name in "ABC"}
+        nnz = sum(int(e.sum()) for e in entries.values())
+        nnz_template = sum(int(e[f:f + R].sum()) for e in entries.values() for f, R in fam)
+        nnz_family = sum(int(e[f:f + K * R].sum()) for e in entries.values() for f, R in fam)
+        out = {"metric": "r1cs_check_compact_multi", "n": n, "n_pairs": K, "steps": a.steps, "legs_agree_and_satisfied": same, "n_constraints": nc,
+               "families": len(fam), "family_rows_share": round(fam_rows / nc, 4), "families_host_s": round(t_fam, 2), "host_matrices_s": round(t_mats, 2),
+               "compact_bytes_per_step": int(lay.total), "expanded_bytes_per_step": int(mats["n_witness"]) * 48 * n,
+               # what each route moves, ESTIMATED from the buffers' sizes (no counter is read): (a) reads the buffer, writes and reads back the vectors; (b) and (c) read the buffer
+               "bytes_estimated_expand_then_check": int(lay.total) + 2 * int(mats["n_witness"]) * 48 * n, "bytes_estimated_check_compact": int(lay.total),
+               # matrix entries a wave walks per group of lanes: every entry (a, c); the templates once plus the rows outside the families (b)
+               "entries_general": nnz, "entries_check_compact": nnz - nnz_family + nnz_template}
+        out.update({k: stats(v, n) for k, v in ms.items()})
+        for k in ("check_compact", "check_compact_general"):
+            out[k + "_over_expand_then_check"] = round(out[k]["median_ms"] / out["expand_then_check"]["median_ms"], 3)
+        print(json.dumps(out), flush=True)
+        ok = ok and same
+    if not ok:
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=None, help="instances per batch / step: 1024, with --keyset 128 (the step of tools/agg_shared_rate.py)")
@@ -222,13 +311,18 @@ def main():
     ap.add_argument("--eval-rows", type=int, default=20000, help="--compact: rows of the evaluate window (the pairing tail)")
     ap.add_argument("--keyset", action="store_true", help="a shared-keys compact step: expand + check against the compact-keyset checks (see the module docstring)")
     ap.add_argument("--keys", type=int, default=512, help="--keyset: keys of the committee")
-    ap.add_argument("--limit", type=float, default=240.0, help="--keyset: seconds per GPU step")
+    ap.add_argument("--limit", type=float, default=240.0, help="--keyset, --multi: seconds per GPU step")
+    ap.add_argument("--multi", action="store_true", help="a compact step of the N+1-pair product: expand + check against the compact check with and without families")
+    ap.add_argument("--pairs", type=int, default=16, help="--multi: pairs per instance")
+    ap.add_argument("--multi-n", default="4,64", help="--multi: step sizes, comma separated (n * pairs a multiple of 64, n a divisor or multiple of 64)")
     a = ap.parse_args()
     a.n = a.n or (128 if a.keyset else 1024)
     if a.compact:
         return compact_legs(a)
     if a.keyset:
         return keyset_legs(a)
+    if a.multi:
+        return multi_legs(a)
     import torch
 
     pkg = importlib.import_module("bls-verify-gadget_amd")
