@@ -153,6 +153,14 @@ def lib():
         L.blsw_verify_groups_batch.argtypes = [vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, u64, vp]
         L.blsw_committee_verify_workspace_bytes.argtypes = [u64, u32, u32, u32, ctypes.POINTER(u64)]
         L.blsw_committee_verify_batch.argtypes = [vp, u32, vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]
+        L.blsw_registry_bytes.argtypes = [u32, ctypes.POINTER(u64)]
+        L.blsw_registry_create.argtypes = [ctypes.POINTER(vp), u32, ctypes.c_int32, vp, u64]
+        L.blsw_registry_append.argtypes = [vp, vp, u32, vp]
+        L.blsw_registry_size.argtypes = [vp, ctypes.POINTER(u32)]
+        L.blsw_registry_key_status.argtypes = [vp, ctypes.POINTER(vp)]
+        L.blsw_registry_destroy.argtypes = [vp]
+        L.blsw_registry_verify_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_registry_verify_batch.argtypes = [vp, vp, u64, vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, vp, u64, vp]
         L.blsw_microbench.argtypes = [ctypes.c_int, u32, u32, ctypes.POINTER(ctypes.c_double)]
         L.blsw_fill_rate.argtypes = [vp, u64, u32, ctypes.POINTER(ctypes.c_double)]
         mi, mp = ctypes.POINTER(blsw_matrices_info_t), ctypes.POINTER(blsw_matrices_t)
@@ -208,7 +216,9 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_r1cs_check_compact_keyset", "blsw_r1cs_evaluate_compact_keyset", "blsw_layout_multi_inputs", "blsw_matrices_info_multi_inputs",
                     "blsw_matrices_fill_multi_inputs", "blsw_engine_submit_multi_io", "blsw_engine_workspace_bytes_multi_inputs", "blsw_engine_create_multi_inputs",
                     "blsw_compact_layout_multi", "blsw_compact_locate_multi", "blsw_compact_locate_multi_range", "blsw_r1cs_pair_families",
-                    "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi"]
+                    "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi",
+                    "blsw_registry_bytes", "blsw_registry_create", "blsw_registry_append", "blsw_registry_size", "blsw_registry_key_status", "blsw_registry_destroy",
+                    "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -1130,6 +1140,135 @@ def committee_verify_grouped(pks48, bitmap, msg, sig96, group=64, scalars=None, 
     bad = torch.nonzero(res == 0).flatten()  # the synchronisation
     if bad.numel():
         res[bad] = committee_verify(pks48, bitmap[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous())
+    return (res, st) if want_status else res
+
+
+REGISTRY_LANES = _header_define("BLSW_REGISTRY_LANES")  # lanes that share one set's key sum
+ST_BAD_INDEX = _header_define("BLSW_ST_BAD_INDEX")
+
+
+class KeyRegistry:
+    """A resident registry of public keys (blsw_registry_*, include/blsw.h): room for `capacity` keys (1 .. 2^24) in a device buffer this object
+    owns; append() decodes compressed keys ONCE, with the subgroup check, on the current stream of `device`, and registry_verify sums index lists
+    over them. A verify call must be ordered behind the appends it relies on (the same stream does that); the object is not thread-safe."""
+
+    def __init__(self, capacity, device=None):
+        torch = _require_cuda()
+        self.capacity = int(capacity)
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        if self.device.index is None:  # "cuda": the current device, with its index, so that it compares equal to the tensors' devices
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        b = ctypes.c_uint64(0)
+        rc = lib().blsw_registry_bytes(self.capacity, ctypes.byref(b))
+        if rc:
+            raise BlswError("blsw_registry_bytes failed: %d" % rc)
+        self.buffer = torch.empty(b.value, dtype=torch.uint8, device=self.device)  # the allocator's blocks are 512-byte aligned
+        self._r = ctypes.c_void_p()
+        rc = lib().blsw_registry_create(ctypes.byref(self._r), self.capacity, self.device.index, self.buffer.data_ptr(), self.buffer.numel())
+        if rc:
+            self._r = None
+            raise BlswError("blsw_registry_create failed: %d" % rc)
+        ptr = ctypes.c_void_p()
+        rc = lib().blsw_registry_key_status(self._r, ctypes.byref(ptr))
+        off = (ptr.value or 0) - self.buffer.data_ptr()
+        if rc or off < 0 or off + 4 * self.capacity > self.buffer.numel():
+            raise BlswError("blsw_registry_key_status failed: %d" % rc)
+        self._status = self.buffer[off:off + 4 * self.capacity].view(torch.int32)
+
+    def append(self, pks48):
+        """uint8 cuda tensor [m, 48] of compressed keys -> they become keys [size, size + m); returns the new size"""
+        torch = _require_cuda()
+        assert pks48.dim() == 2 and pks48.shape[1] == 48 and pks48.dtype == torch.uint8 and pks48.is_contiguous() and pks48.device == self.device
+        rc = lib().blsw_registry_append(self._r, pks48.data_ptr(), pks48.shape[0], torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            raise BlswError("blsw_registry_append failed: %d" % rc)
+        return self.size
+
+    @property
+    def size(self):
+        n = ctypes.c_uint32(0)
+        rc = lib().blsw_registry_size(self._r, ctypes.byref(n))
+        if rc:
+            raise BlswError("blsw_registry_size failed: %d" % rc)
+        return n.value
+
+    def key_status(self):
+        """int32 [size] view of the keys' statuses, defined once the appends have run on their stream"""
+        return self._status[:self.size]
+
+    def close(self):
+        if getattr(self, "_r", None):
+            lib().blsw_registry_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=None, want_status=False, want_aggregate=False):
+    """fast_aggregate_verify as values over a KeyRegistry and n index lists (blsw_registry_verify_batch, include/blsw.h): set i is
+    indices[offsets[i]:offsets[i + 1]] — indices a cuda tensor [n_indices] of 32-bit integers (int32 storage of the uint32 indices), offsets [n + 1]
+    of 64-bit integers; uint8 cuda tensors msg [n, msg_len], sig96 [n, 96]. A repeated index is added as often as it occurs.
+    group == 0 -> int32 [n]: the verdict of fast_aggregate_verify_batch on the gathered keys (an empty list, a bad entry and an identity sum are
+    false). group >= 1 -> int32 [ceil(n / group)]: verify_groups' statement over the sets' sums; scalars None draws coefficients as verify_groups does.
+    Returns the verdicts, or a tuple of them followed by what was asked for, in this order: status [n, 2] int32 ([i, 0] of the set's key —
+    ST_BAD_INDEX for bad offsets or an index >= registry.size —, [i, 1] of the signature), aggregate [n, 48] uint8."""
+    torch = _require_cuda()
+    n, msg_len, n_indices = msg.shape[0], msg.shape[1], indices.shape[0]
+    assert indices.dim() == 1 and offsets.shape == (n + 1,) and sig96.shape == (n, 96)
+    assert indices.element_size() == 4 and offsets.element_size() == 8 and not indices.is_floating_point() and not offsets.is_floating_point()
+    assert all(t.is_contiguous() and t.device == registry.device for t in (indices, offsets, msg, sig96)) and msg.dtype == torch.uint8 and sig96.dtype == torch.uint8
+    dev = registry.device
+    if group and scalars is None:
+        scalars = _group_scalars(torch, n, dev)
+    if scalars is not None:
+        assert scalars.shape == (n,) and scalars.element_size() == 8 and not scalars.is_floating_point() and scalars.is_contiguous() and scalars.device == dev
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_registry_verify_workspace_bytes(n, msg_len, group, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_registry_verify_workspace_bytes failed: %d" % rc)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    res = torch.empty((n + group - 1) // group if group else n, dtype=torch.int32, device=dev)
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    agg = torch.empty((n, 48), dtype=torch.uint8, device=dev) if want_aggregate else None
+    rc = lib().blsw_registry_verify_batch(registry._r, indices.data_ptr() if n_indices else None, n_indices, offsets.data_ptr(), sig96.data_ptr(),
+                                          msg.data_ptr() if msg_len else None, msg_len, n, scalars.data_ptr() if scalars is not None else None, group, res.data_ptr(),
+                                          status.data_ptr(), agg.data_ptr() if want_aggregate else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_registry_verify_batch failed: %d" % rc)
+    extra = ([status] if want_status else []) + ([agg] if want_aggregate else [])
+    return (res, *extra) if extra else res
+
+
+def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, scalars=None, want_status=False):
+    """registry_verify(group=0)'s per-set verdicts through the grouped form: the sets of passing groups are 1; the sets of failing groups are
+    re-checked with the per-set form and scattered back. CSR is one run of n + 1 offsets and the failing sets' lists are not adjacent, so their
+    entries are gathered into an index list of their own. ONE host synchronisation: the group verdicts and the n + 1 offsets come to the host in a
+    single transfer, and the gather positions are laid out there. Like committee_verify_grouped it is slower than the plain call when most groups
+    fail."""
+    torch = _require_cuda()
+    import numpy as np
+
+    n, dev = msg.shape[0], msg.device
+    gres, st = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True)
+    res = gres.repeat_interleave(group)[:n].contiguous()
+    host = torch.cat([res.to(torch.int64), offsets.view(torch.int64)]).cpu().numpy()  # the synchronisation
+    bad = np.flatnonzero(host[:n] == 0)
+    if len(bad):
+        # A set whose offsets are bad becomes the empty list: false again (the statuses returned are the first call's), and nothing of it is read.
+        off = host[n:]  # int64: an offset of 2^63 or more is negative here, and bad
+        lo, hi = off[bad], off[bad + 1]
+        ok = (lo >= 0) & (hi >= lo) & (hi <= indices.shape[0])
+        ln = np.where(ok, hi - lo, 0)
+        ends = np.cumsum(ln)
+        pos = np.arange(ends[-1], dtype=np.int64) + np.repeat(lo - (ends - ln), ln)
+        sub_idx = indices[torch.from_numpy(pos).to(dev)].contiguous()
+        sub_off = torch.from_numpy(np.concatenate([np.zeros(1, np.int64), ends])).to(dev)
+        bad_t = torch.from_numpy(bad).to(dev)
+        res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg[bad_t].contiguous(), sig96[bad_t].contiguous())
     return (res, st) if want_status else res
 
 

@@ -1451,6 +1451,109 @@ int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const u
                              reinterpret_cast<Fp*>(base + f.g.lines_g), reinterpret_cast<Fp*>(base + f.g.partials), d_result, st);
     return hip_ok(hipGetLastError(), "launch");
 }
+// ---- a resident key registry and index lists (include/blsw.h; registry.hpp). The caller's buffer: [capacity] 128-byte records, then the status
+// array [capacity] int32, each 256-byte aligned. `size` lives on the host: a call passes it to its kernel, which reads no record at or beyond it.
+struct blsw_registry {
+    uint32_t capacity = 0, size = 0;
+    int device = -1;
+    char* records = nullptr;
+    int32_t* key_status = nullptr;
+};
+#define BLSW_REGISTRY_MAX_CAPACITY (1u << 24)
+#define BLSW_REGISTRY_RECORD_BYTES 128ull
+static uint64_t registry_offsets(uint32_t capacity, uint64_t* off_status) {
+    *off_status = align_up(capacity * BLSW_REGISTRY_RECORD_BYTES, 256);
+    return *off_status + align_up((uint64_t)capacity * sizeof(int32_t), 256);
+}
+int blsw_registry_bytes(uint32_t capacity, uint64_t* bytes) {
+    if (!bytes || capacity == 0 || capacity > BLSW_REGISTRY_MAX_CAPACITY) return BLSW_ERR_ARG;
+    uint64_t off_status;
+    *bytes = registry_offsets(capacity, &off_status);
+    return BLSW_OK;
+}
+int blsw_registry_create(blsw_registry_t** out, uint32_t capacity, int32_t device, void* d_buffer, uint64_t buffer_bytes) {
+    uint64_t need = 0, off_status = 0;
+    if (!out || !d_buffer || blsw_registry_bytes(capacity, &need) || buffer_bytes < need || (reinterpret_cast<uintptr_t>(d_buffer) & 255)) return BLSW_ERR_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BLSW_ERR_NO_DEVICE;
+    int dev = device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return BLSW_ERR_NO_DEVICE;
+    if (dev >= ndev) return BLSW_ERR_ARG;
+    registry_offsets(capacity, &off_status);
+    blsw_registry* r = new blsw_registry();
+    r->capacity = capacity;
+    r->device = dev;
+    r->records = reinterpret_cast<char*>(d_buffer);
+    r->key_status = reinterpret_cast<int32_t*>(r->records + off_status);
+    *out = r;
+    return BLSW_OK;
+}
+int blsw_registry_append(blsw_registry_t* r, const uint8_t* d_pks48, uint32_t count, void* stream_) {
+    if (!r || !d_pks48 || count == 0 || count > r->capacity - r->size) return BLSW_ERR_ARG;
+    DeviceGuard guard(r->device);
+    launch_registry_append(d_pks48, r->size, count, r->records, r->key_status, reinterpret_cast<hipStream_t>(stream_));
+    if (hip_ok(hipGetLastError(), "launch")) return BLSW_ERR_HIP;
+    r->size += count;
+    return BLSW_OK;
+}
+int blsw_registry_size(const blsw_registry_t* r, uint32_t* n_keys) {
+    if (!r || !n_keys) return BLSW_ERR_ARG;
+    *n_keys = r->size;
+    return BLSW_OK;
+}
+int blsw_registry_key_status(const blsw_registry_t* r, const int32_t** d_status) {
+    if (!r || !d_status) return BLSW_ERR_ARG;
+    *d_status = r->key_status;
+    return BLSW_OK;
+}
+int blsw_registry_destroy(blsw_registry_t* r) {
+    if (!r) return BLSW_ERR_ARG;
+    delete r;
+    return BLSW_OK;
+}
+// Workspace of a verify call: what the chosen verifier's offsets lay out (pk_xy holds the sets' sums), then the hash's carve
+static uint64_t registry_verify_offsets(uint64_t n, uint32_t group, CommitteeOffsets* f) {
+    f->table = 0;  // none: the table lives in the handle
+    if (group == 0) return verify_offsets(n, &f->pk, &f->sig, &f->ls, &f->lh);
+    const uint64_t o = verify_groups_offsets(n, group, &f->g);
+    f->pk = f->g.pk;
+    f->sig = f->g.sig;
+    return o;
+}
+static bool registry_shape_ok(uint64_t n, uint32_t msg_len, uint32_t group) { return n != 0 && n <= 0x7fffffffu && msg_len <= 65535 && group <= 65535; }
+int blsw_registry_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t group, uint64_t* bytes) {
+    if (!bytes || !registry_shape_ok(n, msg_len, group)) return BLSW_ERR_ARG;
+    CommitteeOffsets f;
+    *bytes = direct_values_bytes(n, msg_len, registry_verify_offsets(n, group, &f));
+    return BLSW_OK;
+}
+int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96, const uint8_t* d_msg,
+                               uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status, uint8_t* d_agg48, void* d_workspace,
+                               uint64_t workspace_bytes, void* stream_) {
+    if (!registry_shape_ok(n, msg_len, group) || !d_sig96 || (!d_msg && msg_len) || !d_result || !d_status || !d_workspace ||
+        (group == 0 ? d_scalars != nullptr : d_scalars == nullptr) || !r || !d_offsets || (!d_indices && n_indices) || n_indices > (1ull << 40) || r->size == 0)
+        return BLSW_ERR_ARG;
+    CommitteeOffsets f;
+    const uint64_t off_ws = registry_verify_offsets(n, group, &f);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    uint64_t* pk_xy = reinterpret_cast<uint64_t*>(base + f.pk);
+    uint64_t* sig_xy = reinterpret_cast<uint64_t*>(base + f.sig);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(r->device);
+    Group g;
+    if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
+    launch_committee_decode(nullptr, 0, d_sig96, n, nullptr, nullptr, sig_xy, d_status, st);  // no keys: its n signature lanes alone, status[i][1]
+    launch_registry_sum(r->records, r->size, d_indices, n_indices, d_offsets, n, pk_xy, d_status, d_agg48, st);
+    launch_values_hash(g, st);
+    if (group == 0)
+        launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + f.ls), reinterpret_cast<Fp*>(base + f.lh), d_status, d_result, st);
+    else
+        launch_verify_groups(n, group, BLSW_VGROUP_CHUNK, g.ws, pk_xy, sig_xy, d_status, d_scalars, reinterpret_cast<Fp*>(base + f.g.p_scaled), reinterpret_cast<Fp*>(base + f.g.s_scaled),
+                             reinterpret_cast<Fp*>(base + f.g.sum), reinterpret_cast<int32_t*>(base + f.g.gflag), reinterpret_cast<Fp*>(base + f.g.lines_h),
+                             reinterpret_cast<Fp*>(base + f.g.lines_g), reinterpret_cast<Fp*>(base + f.g.partials), d_result, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
 // BLS::sign + PublicKey::from(&sk) for a batch (bls.rs:411-425, 183-195). Workspace: blsw_hash_to_g2_workspace_bytes.
 int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
                     uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {

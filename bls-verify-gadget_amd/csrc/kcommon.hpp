@@ -851,6 +851,11 @@ void launch_committee_decode(const uint8_t* pks48, uint32_t n_keys, const uint8_
                              hipStream_t st);
 void launch_committee_sum(const uint8_t* bitmap, uint32_t n_keys, uint64_t n, const Fp* table, const int32_t* key_status, uint64_t* pk_xy, int32_t* status, uint32_t* count,
                           uint8_t* agg48, hipStream_t st);
+// blsw_registry_* (k_registry.hip, registry.hpp): keys [first, first + count) decoded into the handle's 128-byte records and its status array; then
+// per set the sum of the records its index list names, checked against `size` -> pk_xy [n][12], status[i][0], agg48 (nullable)
+void launch_registry_append(const uint8_t* pks48, uint32_t first, uint32_t count, void* records, int32_t* key_status, hipStream_t st);
+void launch_registry_sum(const void* records, uint32_t size, const uint32_t* indices, uint64_t n_indices, const uint64_t* offsets, uint64_t n, uint64_t* pk_xy, int32_t* status,
+                         uint8_t* agg48, hipStream_t st);
 
 }  // namespace blsw
 

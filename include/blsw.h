@@ -39,6 +39,7 @@ extern "C" {
 #define BLSW_ST_NOT_IN_SUBGROUP 3
 #define BLSW_ST_IDENTITY 4
 #define BLSW_ST_INVALID_SECRET_KEY 5
+#define BLSW_ST_BAD_INDEX 6 /* blsw_registry_verify_batch: offsets that describe no list, or an index at or beyond the registry's size */
 
 /* Segment table of one instance's witness vector for the circuit of src/constraints.rs:335-366
  * (msg witness bytes, params Constant, pk Witness, sig Witness, then verify). Offsets are in field elements.
@@ -733,6 +734,55 @@ int blsw_committee_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t
 int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const uint8_t* d_bitmap, const uint8_t* d_sig96, const uint8_t* d_msg,
                                 uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, uint32_t* d_count,
                                 int32_t* d_status, int32_t* d_key_status, uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* fast_aggregate_verify as VALUES over a RESIDENT registry of keys and n INDEX LISTS, the shape of a consensus client's signature sets: (a list of
+ * validator indices, one message, one aggregate signature) over 10^5 .. 10^6 keys that change only by appending. New symbols only: the ABI number
+ * stays 17. A committee of that size cannot be decoded inside the call (and a bitmap row per set would be n * K bytes), so the keys get a handle:
+ * they are decoded ONCE, when appended, into 128-byte records (x, y, status: one cache line per gathered key; csrc/registry.hpp) that stay in the
+ * caller's device buffer, and a call sums each list's records with BLSW_REGISTRY_LANES lanes and hands the sums to the two verifiers above unchanged.
+ * The handle follows the conventions of blsw_keyset_create: the caller owns d_buffer (256-byte aligned, blsw_registry_bytes(capacity) bytes), which
+ * must outlive the handle and every call that names it; device -1 = the current device; every rule is checked on the host before any HIP call.
+ *   blsw_registry_create: an empty registry of room for `capacity` keys, 1 .. 2^24 (16 777 216). Nothing is launched; the buffer is not cleared.
+ *   blsw_registry_append: d_pks48 [count][48] compressed keys become keys [size, size + count): decoded with the subgroup check, one lane per key,
+ *     asynchronously on `stream`. size grows ON THE HOST AT THE CALL. BLSW_ERR_ARG: a NULL handle or d_pks48, count == 0, size + count > capacity.
+ *   blsw_registry_size: the number of keys appended so far.
+ *   blsw_registry_key_status: the device array [capacity] int32 of the keys' BLSW_ST_*; entries [0, size) are defined once their appends have run.
+ *   blsw_registry_destroy: frees the handle; the buffer is the caller's.
+ * A verify call must be ORDERED BEHIND the appends it relies on (the same stream, or an event): it reads records the appends write. The handle is
+ * NOT thread-safe: append, size and verify calls on one handle must not run concurrently.
+ *   blsw_registry_verify_batch: set i is d_indices[d_offsets[i] .. d_offsets[i + 1]) — CSR, d_offsets [n + 1] uint64, d_indices [n_indices] uint32.
+ *   d_sig96 [n][96], d_msg [n][msg_len]; d_status [n][2] int32: [i][1] the signature's status as blsw_verify_batch writes it; [i][0], in this order:
+ *     1. BLSW_ST_BAD_INDEX if d_offsets[i] > d_offsets[i + 1] or d_offsets[i + 1] > n_indices (or the list is longer than 2^32 - 2 entries): no
+ *        entry of the set is read;
+ *     2. else the status of the EARLIEST LIST POSITION whose entry is bad — an index >= size as of the call is BLSW_ST_BAD_INDEX (also one below
+ *        capacity that is not yet appended: its row is never read, so no stale row can count), a key whose status is neither OK nor IDENTITY
+ *        gives that status;
+ *     3. else BLSW_ST_IDENTITY if the sum is the identity (the empty list included);  4. else BLSW_ST_OK.
+ *     A repeated index is added as often as it occurs; a selected identity key is a valid summand (PublicKey::aggregate, src/bls.rs:183-195).
+ *   d_agg48 [n][48] (nullable): byte for byte what blsw_aggregate_points_batch(1, ...) gives for the gathered keys in list order (the infinity
+ *     encoding for the identity and the empty list); zeros when the set has a bad entry or bad offsets.
+ *   group == 0 / group >= 1, d_scalars and the length of d_result: word for word as blsw_committee_verify_batch — per set the verdict of
+ *     blsw_verify_batch on (d_agg48[i], msg_i, sig_i), 0 whenever d_status[i][0] is not OK; or blsw_verify_groups_batch's statement and its
+ *     properties P1-P4 with pk_i = the set's sum and its status = d_status[i][0].
+ * BLSW_ERR_ARG before any HIP call, nothing written: n == 0 or > 0x7fffffff, msg_len > 65535, group > 65535, a NULL among r, d_offsets, d_sig96,
+ *   d_result, d_status, d_workspace, d_scalars non-NULL with group == 0 or NULL with group >= 1, d_msg == NULL with msg_len != 0, d_indices == NULL
+ *   with n_indices != 0, n_indices > 2^40, a registry of size 0. BLSW_ERR_WORKSPACE for a workspace below
+ *   blsw_registry_verify_workspace_bytes(n, msg_len, group): what the chosen verifier's workspace holds and the hash's carve — no table, it lives in
+ *   the handle. Asynchronous on `stream` (a stream of the handle's device) after the one synchronising descriptor copy the two verifiers make. */
+#ifndef BLSW_REGISTRY_LANES
+#define BLSW_REGISTRY_LANES 16 /* lanes that share one set's sum; a power of two <= 64. Measured (profiles/registry_rate.txt): at K = 512, n = 8 192 16 is lowest (4 .. 64 within 3 %); at 2^20 keys, n = 2 048 sets of 400 - 500 and 1 indices 32 is lowest and 16 lies 0.5 % above it */
+#endif
+typedef struct blsw_registry blsw_registry_t;
+int blsw_registry_bytes(uint32_t capacity, uint64_t* bytes);
+int blsw_registry_create(blsw_registry_t** out, uint32_t capacity, int32_t device, void* d_buffer, uint64_t buffer_bytes);
+int blsw_registry_append(blsw_registry_t* r, const uint8_t* d_pks48, uint32_t count, void* stream);
+int blsw_registry_size(const blsw_registry_t* r, uint32_t* n_keys);
+int blsw_registry_key_status(const blsw_registry_t* r, const int32_t** d_status); /* [capacity], entries [0, size) defined */
+int blsw_registry_destroy(blsw_registry_t* r);
+int blsw_registry_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t group, uint64_t* bytes);
+int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96,
+                               const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status,
+                               uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* Device micro-benchmarks that give the VALU roofline its MEASURED denominator:
  * which = 0: v_mad_u64_u32 rate (32x32+64 multiply-adds per second, all CUs); 1: Fp Montgomery products per second;

@@ -166,6 +166,81 @@ struct Signature {
     }
 };
 
+// A resident registry of public keys (blsw_registry_t): room for `capacity` keys (1 .. 2^24), decoded ONCE when they are appended — with the
+// subgroup check, asynchronously on the stream given — and summed through index lists by BLS::fast_aggregate_verify_indexed. Owns the handle and
+// its device buffer. A verify call must be ordered behind the appends it relies on; the object is not thread-safe.
+class KeyRegistry {
+   public:
+    explicit KeyRegistry(uint32_t capacity, int device = -1) : capacity_(capacity), device_(device) {
+        uint64_t bytes = 0;
+        check(blsw_registry_bytes(capacity, &bytes), "blsw_registry_bytes");
+        if (device_ < 0) hip_check(hipGetDevice(&device_), "hipGetDevice");
+        const OnDevice on(device_);
+        buffer_ = detail::DeviceBytes(bytes);  // hipMalloc: 256-byte aligned
+        check(blsw_registry_create(&r_, capacity, device_, buffer_.get(), bytes), "blsw_registry_create");
+    }
+    KeyRegistry(const KeyRegistry&) = delete;
+    KeyRegistry& operator=(const KeyRegistry&) = delete;
+    KeyRegistry(KeyRegistry&& o) noexcept : r_(o.r_), capacity_(o.capacity_), device_(o.device_), buffer_(std::move(o.buffer_)) { o.r_ = nullptr; }
+    ~KeyRegistry() {
+        if (r_) (void)blsw_registry_destroy(r_);
+    }
+    const blsw_registry_t* get() const { return r_; }
+    uint32_t capacity() const { return capacity_; }
+    uint32_t size() const {
+        uint32_t n = 0;
+        check(blsw_registry_size(r_, &n), "blsw_registry_size");
+        return n;
+    }
+    // d_pks48 [count][48] compressed keys on the device become keys [size, size + count)
+    void append_device(const uint8_t* d_pks48, uint32_t count, void* stream = nullptr) { check(blsw_registry_append(r_, d_pks48, count, stream), "blsw_registry_append"); }
+    // host keys: uploaded, appended on the NULL stream, and waited for (the staging copy is released on return)
+    void append(const std::vector<PublicKey>& keys) {
+        if (keys.empty()) return;
+        std::vector<uint8_t> pk(keys.size() * 48);
+        for (size_t k = 0; k < keys.size(); k++) std::memcpy(&pk[48 * k], keys[k].bytes.data(), 48);
+        const OnDevice on(device_);
+        detail::DeviceBytes d(pk.size());
+        d.upload(pk.data(), pk.size());
+        append_device(static_cast<const uint8_t*>(d.get()), (uint32_t)keys.size());
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    // the keys' BLSW_ST_* [size], downloaded (waits for the device)
+    std::vector<int32_t> key_status() const {
+        const int32_t* d = nullptr;
+        check(blsw_registry_key_status(r_, &d), "blsw_registry_key_status");
+        std::vector<int32_t> st(size());
+        const OnDevice on(device_);
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        if (!st.empty()) hip_check(hipMemcpy(st.data(), d, st.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        return st;
+    }
+
+    int device() const { return device_; }
+
+   private:
+    // the registry's device made current for a scope; the caller's current device is as it was afterwards, also when the scope throws
+    struct OnDevice {
+        int prev = -1;
+        explicit OnDevice(int device) {
+            int cur = -1;
+            hip_check(hipGetDevice(&cur), "hipGetDevice");
+            if (cur == device) return;
+            hip_check(hipSetDevice(device), "hipSetDevice");
+            prev = cur;
+        }
+        OnDevice(const OnDevice&) = delete;
+        OnDevice& operator=(const OnDevice&) = delete;
+        ~OnDevice() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    };
+    blsw_registry_t* r_ = nullptr;
+    uint32_t capacity_ = 0;
+    int device_ = -1;
+    detail::DeviceBytes buffer_;
+};
+
 // n independent constraint systems of one circuit shape (constraints.rs:335: `ConstraintSystem::<Fq>::new_ref()`, once per instance there)
 class ConstraintSystem {
    public:
@@ -1023,6 +1098,89 @@ struct BLS {
             s2.push_back(sigs[i]);
         }
         const std::vector<bool> r = fast_aggregate_verify_committee(params, committee, b2, m2, s2);
+        for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
+        return out;
+    }
+    // fast_aggregate_verify over a resident KeyRegistry and one list of key INDICES per set (blsw_registry_verify_batch, include/blsw.h): a repeated
+    // index is added as often as it occurs. group == 0: one verdict per set — true iff the list is not empty, every index is below registry.size(),
+    // every named key decodes, the sum is not the identity and BLS::verify accepts it. group >= 1: one verdict per group of sets, verify_groups'
+    // statement over the sums; scalars as there (empty draws group_scalars(n); ignored for group == 0).
+    // status [n][2] (the set's key — BLSW_ST_BAD_INDEX for an index >= size —, signature) and aggregates [n] (the compressed sums) are filled when given.
+    static std::vector<bool> fast_aggregate_verify_indexed(const Parameters&, const KeyRegistry& registry, const std::vector<std::vector<uint32_t>>& index_lists,
+                                                           const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& sigs, uint32_t group = 0,
+                                                           std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr,
+                                                           std::vector<PublicKey>* aggregates = nullptr) {
+        const size_t n = index_lists.size();
+        if (n == 0 || messages.size() != n || sigs.size() != n)
+            throw Error("BLS::fast_aggregate_verify_indexed: one index list, message and signature per set", BLSW_ERR_ARG);
+        if (group) {
+            if (scalars.empty()) scalars = group_scalars(n);
+            if (scalars.size() != n) throw Error("BLS::fast_aggregate_verify_indexed: one coefficient per set", BLSW_ERR_ARG);
+        }
+        const uint32_t msg_len = (uint32_t)messages[0].size();
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) off[i + 1] = off[i] + index_lists[i].size();
+        std::vector<uint32_t> idx(off[n]);
+        std::vector<uint8_t> sg(n * 96), msg(n * (size_t)msg_len);
+        for (size_t i = 0; i < n; i++) {
+            if (messages[i].size() != msg_len) throw Error("BLS::fast_aggregate_verify_indexed: messages of one length per batch", BLSW_ERR_ARG);
+            if (!index_lists[i].empty()) std::memcpy(&idx[off[i]], index_lists[i].data(), index_lists[i].size() * 4);
+            std::memcpy(&sg[96 * i], sigs[i].bytes.data(), 96);
+            if (msg_len) std::memcpy(&msg[(size_t)msg_len * i], messages[i].data(), msg_len);
+        }
+        const size_t n_res = group ? (n + group - 1) / group : n;
+        uint64_t bytes = 0;
+        check(blsw_registry_verify_workspace_bytes(n, msg_len, group, &bytes), "blsw_registry_verify_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_idx(idx.size() * 4), d_off(off.size() * 8), d_sg(sg.size()), d_msg(msg.size()), d_sc(n * 8), d_st(n * 8), d_agg(n * 48), d_res(n_res * 4);
+        if (!idx.empty()) d_idx.upload(idx.data(), idx.size() * 4);
+        d_off.upload(off.data(), off.size() * 8);
+        d_sg.upload(sg.data(), sg.size());
+        if (group) d_sc.upload(scalars.data(), n * 8);
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        check(blsw_registry_verify_batch(registry.get(), idx.empty() ? nullptr : static_cast<const uint32_t*>(d_idx.get()), idx.size(), static_cast<const uint64_t*>(d_off.get()),
+                                         static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
+                                         group ? static_cast<const uint64_t*>(d_sc.get()) : nullptr, group, static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()),
+                                         static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, nullptr),
+              "blsw_registry_verify_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n_res);
+        d_res.download(r.data(), n_res * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
+        }
+        if (aggregates) {
+            std::vector<uint8_t> a(n * 48);
+            d_agg.download(a.data(), a.size());
+            aggregates->resize(n);
+            for (size_t i = 0; i < n; i++) std::memcpy((*aggregates)[i].bytes.data(), &a[48 * i], 48);
+        }
+        std::vector<bool> out(n_res);
+        for (size_t j = 0; j < n_res; j++) out[j] = r[j] == 1;
+        return out;
+    }
+    // the per-set verdicts through groups: the sets of passing groups are true, those of failing groups go through the per-set form once more (the
+    // registry is not decoded again: it is resident). Slower than group == 0 when most groups hold a bad set.
+    static std::vector<bool> fast_aggregate_verify_indexed_grouped(const Parameters& params, const KeyRegistry& registry, const std::vector<std::vector<uint32_t>>& index_lists,
+                                                                   const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& sigs, uint32_t group = 64,
+                                                                   std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr) {
+        if (group == 0) throw Error("BLS::fast_aggregate_verify_indexed_grouped: group >= 1", BLSW_ERR_ARG);
+        const std::vector<bool> g = fast_aggregate_verify_indexed(params, registry, index_lists, messages, sigs, group, std::move(scalars), status);
+        const size_t n = index_lists.size();
+        std::vector<bool> out(n, true);
+        std::vector<size_t> idx;
+        for (size_t i = 0; i < n; i++)
+            if (!g[i / group]) idx.push_back(i);
+        if (idx.empty()) return out;
+        std::vector<std::vector<uint32_t>> l2;
+        std::vector<std::vector<uint8_t>> m2;
+        std::vector<Signature> s2;
+        for (size_t i : idx) {
+            l2.push_back(index_lists[i]);
+            m2.push_back(messages[i]);
+            s2.push_back(sigs[i]);
+        }
+        const std::vector<bool> r = fast_aggregate_verify_indexed(params, registry, l2, m2, s2);
         for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
         return out;
     }

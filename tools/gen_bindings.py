@@ -20,7 +20,7 @@ SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i3
 STRUCT_NAMES = {"blsw_layout_t": "BlswLayout", "blsw_engine_options_t": "BlswEngineOptions", "blsw_engine_t": "BlswEngine",
                 "blsw_matrices_t": "BlswMatrices", "blsw_matrices_info_t": "BlswMatricesInfo",
                 "blsw_r1cs_t": "BlswR1cs", "blsw_compact_layout_t": "BlswCompactLayout", "blsw_compact_layout_multi_t": "BlswCompactLayoutMulti",
-                "blsw_keyset_t": "BlswKeyset"}
+                "blsw_keyset_t": "BlswKeyset", "blsw_registry_t": "BlswRegistry"}
 
 
 def strip_comments(text):
