@@ -19,6 +19,7 @@
 #include "../devteam/ops.hpp"
 #include "../devcurve/ops.hpp"
 #include "../devsha/ops.hpp"
+#include "../devpair/ops.hpp"
 #include <array>
 
 using namespace blsw;
@@ -146,6 +147,24 @@ struct TeamHost {
         for (uint32_t j = 0; j < 6; j++) devteam::st2(out + 2 * j, r[j]);
     }
     void st_flag(bool v) { devteam::st_verdict(out, v); }
+    // what the table of pairing programs (tests/devpair/ops.hpp) adds: the constant of the pair (-g1, sig) in front of team_miller_multi
+    void set_gen_y() { team_st(slots, TS_XYC, {K_G1_GEN_NEG_Y(), fp_zero()}); }
+};
+// the team of the two group entries of tests/devpair/ops.hpp (TeamLanesGroups on the device): pairs [first, first + count) are the item's
+// instance line sets, pair first + count the group's own; a cleared mask bit is a skipped pair; load_partial reads the item's partial products
+struct TeamHostGroupsTable : TeamHost {
+    const Fp* sets = nullptr;      // [9][408]
+    const Fp* partials = nullptr;  // [3][12]
+    uint64_t first = 0;
+    uint32_t count = 0, mask = 0;
+    bool load_pair(uint64_t p, uint32_t k) {
+        const uint32_t rel = (uint32_t)(p - first);
+        if (!((mask >> rel) & 1u)) return false;
+        const CoeffLinear c{const_cast<Fp*>(sets) + rel * BLSW_VLINE_ROWS};
+        for (uint32_t j = 0; j < 6; j++) team_load_pair_lines_lane(j, slots, c, k);
+        return true;
+    }
+    Reg load_partial(uint64_t idx) const { return ld(partials + 12 * idx); }
 };
 static int g_use_team = 0;
 static int g_cofactor_par = 0;  // 1: clear_cofactor2 through cofactor_par.hpp (chunks in the order 2, 0, 1, then the join); 2: cofactor_vf.hpp
@@ -733,6 +752,116 @@ int hostsim_team_op_count() { return devteam::OP_COUNT; }
 int hostsim_team_op_n_wit(int op) { return (int)devteam::op_n_wit(op, devteam::NwTables()); }
 int hostsim_team_op_tail(int op) { return (int)devteam::op_tail(op, devteam::NwTables()); }
 int hostsim_team_op_dual(int op) { return devteam::op_dual(op); }
+// one entry of the table of pairing programs (tests/devpair/ops.hpp: the table tests/devpair/devpair.hip runs on the device) over n items. form 0:
+// the single-lane statement; 1: the program on the looped team above. in [n][n_in][6] u64 operand blocks (hostsim_pair_op_n_in(op, K)); out
+// [n][n_out][6]; wit [n][wcap][6]; npos [n] the cursor after the entry (form 0: the entry's count, its chains take the cursor by value). Returns 0, -1
+// for an unknown entry, form or K, -2 when wcap is below the entry's witness count.
+int hostsim_pair_op(int form, int op, uint32_t K, uint64_t n, const uint64_t* in, uint64_t* out, uint64_t* wit, uint32_t wcap, uint32_t* npos) {
+    const int forms = devpair::op_forms(op);
+    if (forms < 0 || form < 0 || form > 1 || !((forms >> form) & 1) || !devpair::k_ok(op, K)) return -1;
+    const int64_t n_wit = devpair::op_n_wit(op, K, devteam::NwTables()), n_in = devpair::op_n_in(op, K), n_out = devpair::op_n_out(op);
+    if ((int64_t)wcap < n_wit) return -2;
+    for (uint64_t i = 0; i < n; i++) {
+        std::vector<Fp> fin(n_in), fo(n_out);
+        for (int64_t k = 0; k < n_in; k++) fin[k] = load_fp(in + (i * n_in + k) * 6);
+        Emitter e = {reinterpret_cast<uint32_t*>(wit + i * (uint64_t)wcap * 6), 0};
+        if (n_wit == 0) e.base = nullptr;
+        if (form == 0) {
+            devpair::run_single(op, K, fin.data(), fo.data(), e);
+            npos[i] = (uint32_t)n_wit;
+        } else if (op == devpair::OP_miller_groups || op == devpair::OP_groups_finish) {
+            TeamHostGroupsTable t;
+            memset(t.slots, 0, sizeof(t.slots));
+            t.e = {nullptr, 0};
+            if (op == devpair::OP_miller_groups) {
+                t.count = fin[0].l[0];
+                t.mask = fin[2].l[0];
+                t.first = 5 * i;  // any base: the program only forms differences with it
+                t.sets = fin.data() + DEVPAIR_GROUPS_HDR;
+                const TeamHost::Reg f = devpair::run_team<devpair::OP_miller_groups>(t, fp_zero(), fp_zero(), t.count + (fin[1].l[0] ? 1u : 0u));
+                for (uint32_t j = 0; j < 6; j++) devteam::st2(fo.data() + 2 * j, f[j]);
+            } else {
+                t.partials = fin.data() + 1;
+                devteam::st_verdict(fo.data(), devpair::run_team_finish(t, 0, fin[0].l[0]));
+            }
+            npos[i] = t.e.pos;
+        } else {
+            const devpair::PairsBlock pairs = {fin.data()};
+            std::vector<G1ChainOut> pk(K);
+            std::vector<std::vector<Fp>> ch(K);
+            for (uint32_t j = 0; j < K && op != devpair::OP_miller_values; j++) {
+                pairs.pk(j, pk[j].ax, pk[j].ay);
+                ch[j].assign(pairs.coeff_h(j).p, pairs.coeff_h(j).p + DEVPAIR_COEFFS);
+            }
+            TeamHost t;
+            memset(t.slots, 0, sizeof(t.slots));
+            t.e = e;
+            t.pkx = t.pky = fp_zero();
+            t.coeff_sig = CoeffLinear{fin.data()};
+            t.coeff_h = op == devpair::OP_miller_values ? CoeffLinear{fin.data() + BLSW_VLINE_ROWS} : (op == devpair::OP_miller_multi ? CoeffLinear{nullptr} : CoeffLinear{ch[0].data()});
+            t.pair_coeff = &ch;
+            t.pair_pk = &pk;
+            TeamHost::Reg f;
+            switch (op) {
+                case devpair::OP_miller: f = devpair::run_team<devpair::OP_miller>(t, pk[0].ax, pk[0].ay, K); break;
+                case devpair::OP_miller_pv: f = devpair::run_team<devpair::OP_miller_pv>(t, pk[0].ax, pk[0].ay, K); break;
+                case devpair::OP_miller_multi: f = devpair::run_team<devpair::OP_miller_multi>(t, pk[0].ax, pk[0].ay, K); break;
+                default: f = devpair::run_team<devpair::OP_miller_values>(t, fp_zero(), fp_zero(), K); break;
+            }
+            for (uint32_t j = 0; j < 6; j++) devteam::st2(fo.data() + 2 * j, f[j]);
+            npos[i] = t.e.pos;
+        }
+        memcpy(out + i * n_out * 6, fo.data(), (size_t)n_out * sizeof(Fp));
+    }
+    return 0;
+}
+const char* hostsim_pair_op_name(int op) {
+    static const char* const T[devpair::OP_COUNT] = {
+#define HOSTSIM_X_PNAME(name, sdev, team, nin, nout, wit) #name,
+        DEVPAIR_OPS(HOSTSIM_X_PNAME)
+#undef HOSTSIM_X_PNAME
+    };
+    return (op >= 0 && op < devpair::OP_COUNT) ? T[op] : "";
+}
+int hostsim_pair_op_count() { return devpair::OP_COUNT; }
+int hostsim_pair_op_forms(int op) { return devpair::op_forms(op); }
+int64_t hostsim_pair_op_n_wit(int op, uint32_t K) { return devpair::k_ok(op, K) ? devpair::op_n_wit(op, K, devteam::NwTables()) : -1; }
+int64_t hostsim_pair_op_n_in(int op, uint32_t K) { return devpair::k_ok(op, K) ? devpair::op_n_in(op, K) : -1; }
+int64_t hostsim_pair_op_n_out(int op) { return devpair::op_n_out(op); }
+// the two statements of the Miller segment's fixed part: as miller_step_info() places it, and from the op tables' counts
+uint32_t hostsim_pair_spine_witnesses(int from_tables) { return from_tables ? devpair::spine_from_tables(devteam::NwTables()) : devpair::spine_witnesses(); }
+// the four phases of miller_par.hpp (m1, m1b, the single-lane spine m2, m3) over n items of K pairs in chunks of B, the tasks one after the other, on
+// the arrays of the device's launch (element-major Fp12Rows over ALL items): in [n][272 + 274 K][6] operand blocks of miller_multi; ffinal [12][n];
+// f1, t [12][n 68]; q [12][n 68 C], item (i 68 + k) C + c (the caller's sentinel stays where nothing is stored); wit [n][wcap][6]: the Miller
+// segment at cursor 0. Returns 0, -1 for K or B out of range, -2 when wcap is below the segment's length.
+int hostsim_pair_par(uint32_t K, uint32_t B, uint64_t n, const uint64_t* in, uint64_t* ffinal, uint64_t* wit, uint32_t wcap, uint64_t* f1, uint64_t* t, uint64_t* q) {
+    if (K < 1 || K > DEVPAIR_K_MAX || B < 1) return -1;
+    const int64_t n_wit = devpair::op_n_wit(devpair::OP_miller_multi, K, devteam::NwTables()), n_in = devpair::op_n_in(devpair::OP_miller_multi, K);
+    if ((int64_t)wcap < n_wit) return -2;
+    const uint32_t C = miller_chunks(K, B), S = BLSW_MILLER_STEPS;
+    const uint64_t steps = n * S, tasks = steps * C;
+    std::vector<Fp> cprod(12 * tasks);
+    const Fp12Rows Cp = {cprod.data(), tasks}, Q = {reinterpret_cast<Fp*>(q), tasks}, T = {reinterpret_cast<Fp*>(t), steps}, F1 = {reinterpret_cast<Fp*>(f1), steps};
+    const Fp12Rows FF = {reinterpret_cast<Fp*>(ffinal), n};
+    for (uint64_t i = 0; i < n; i++) {
+        std::vector<Fp> fin(n_in);
+        for (int64_t k = 0; k < n_in; k++) fin[k] = load_fp(in + (i * n_in + k) * 6);
+        const devpair::PairsBlock hp = {fin.data()};
+        const Emitter e = {reinterpret_cast<uint32_t*>(wit + i * (uint64_t)wcap * 6), 0};
+        for (uint32_t k = 0; k < S; k++)
+            for (uint32_t c = 0; c < C; c++) Cp.st((i * S + k) * C + c, miller_m1(hp, K, B, k, c));
+        for (uint32_t k = 0; k < S; k++) miller_m1b(Cp, Q, T, (i * S + k) * C, i * S + k, C);
+        FF.st(i, miller_m2(e, K, CoeffLinear{fin.data()}, T, F1, i * S));
+        for (uint32_t k = 0; k < S; k++)
+            for (uint32_t c = 0; c < C; c++) miller_m3(e, hp, K, B, k, c, F1.ld(i * S + k), Q, (i * S + k) * C + c);
+    }
+    return 0;
+}
+// the 272 line coefficients of an affine G2 point (not the identity) by chain_prepare_g2, value only: the operands of the witness entries
+void hostsim_pair_prepare(const uint64_t* q_xy, uint64_t* coeff) {
+    const Proj<OpsFp2> q = {{load_fp(q_xy), load_fp(q_xy + 6)}, {load_fp(q_xy + 12), load_fp(q_xy + 18)}, fp2_one()};
+    chain_prepare_g2(Emitter{nullptr, 0}, q, CoeffLinear{reinterpret_cast<Fp*>(coeff)});
+}
 // one operation of the curve table (tests/devcurve/ops.hpp: the table tests/devcurve/devcurve.hip runs on the device) on one item, with the
 // arrays of hostsim_field_op; the PARK of v_clear_cofactor and v_g2_mul_gls is an array. Returns the witness cursor after the operation, -1 for an
 // unknown operation.

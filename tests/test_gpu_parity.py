@@ -1293,6 +1293,25 @@ def test_verify_multi_pair_parallel_batch(pkg, oracle):
         assert len(bad) == 0, "instance %d: first mismatching witness index %d" % (i, bad[0])
 
 
+@pytest.mark.parametrize("K,tamper", [(7, None), (8, 5), (12, 0), (13, None)])
+def test_verify_multi_at_the_chunk_borders(pkg, oracle, K, tamper):
+    """The product at the borders of the pair-parallel path, one instance each: K = 7 (the largest K of the serial team chain), K = 8
+    (BLSW_MILLER_PAR_MIN_PAIRS: one chunk, no prefix Q[k][c] is ever stored), K = 12 (one full chunk), K = 13 (a second chunk of one
+    pair) — every witness element against the oracle; the oracle's seconds are printed."""
+    import time
+
+    c = synth.make_multi(oracle, K, tamper=tamper, start=3 * K)
+    got, wit = _multi_run(pkg, c[0][None].copy(), c[1][None].copy(), c[2][None].copy())
+    assert got.tolist() == [c[3]] and c[3] == (tamper is None)
+    t0 = time.time()
+    n, res, _, ow = oracle.witness_multi(c[0], c[1], c[2])
+    print("K=%d: oracle.witness_multi %.2f s" % (K, time.time() - t0))
+    w = wit[0].cpu().numpy().view(np.uint64)
+    assert n == w.shape[0] and res == c[3]
+    bad = np.nonzero((ow != w).any(axis=1))[0]
+    assert len(bad) == 0, "K=%d: first mismatching witness index %d" % (K, bad[0])
+
+
 @pytest.mark.parametrize("K,n,consumer", [(3, 2, 0), (20, 3, 0), (20, 2, 1)])
 def test_engine_multi_grouped(pkg, oracle, K, n, consumer):
     """The N+1-pair product through the GROUPED engine (options.n_pairs = K; blsw_engine_submit_multi): pair tiles, instance tiles and
