@@ -151,6 +151,8 @@ def lib():
         L.blsw_verify_batch.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
         L.blsw_verify_groups_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
         L.blsw_verify_groups_batch.argtypes = [vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, u64, vp]
+        L.blsw_verify_pairs_workspace_bytes.argtypes = [u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_verify_pairs_batch.argtypes = [vp, vp, u32, u32, vp, vp, u64, vp, vp, vp, vp, u64, vp]
         L.blsw_committee_verify_workspace_bytes.argtypes = [u64, u32, u32, u32, ctypes.POINTER(u64)]
         L.blsw_committee_verify_batch.argtypes = [vp, u32, vp, vp, vp, u32, u64, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp]
         L.blsw_registry_bytes.argtypes = [u32, ctypes.POINTER(u64)]
@@ -218,7 +220,7 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_compact_layout_multi", "blsw_compact_locate_multi", "blsw_compact_locate_multi_range", "blsw_r1cs_pair_families",
                     "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi",
                     "blsw_registry_bytes", "blsw_registry_create", "blsw_registry_append", "blsw_registry_size", "blsw_registry_key_status", "blsw_registry_destroy",
-                    "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch"]
+                    "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch", "blsw_verify_pairs_workspace_bytes", "blsw_verify_pairs_batch"]
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -1085,6 +1087,43 @@ def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=F
     if bad.numel():
         res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous())
     return (res, status) if want_status else res
+
+
+VERIFY_PAIRS_CHUNK = _header_define("BLSW_VPAIRS_CHUNK")  # pairs of one instance that one six-lane team folds with shared squarings
+
+
+def verify_pairs(pks48, msgs, sig96, counts=None, want_status=False, want_key_status=False):
+    """AggregateVerify as values (blsw_verify_pairs_batch, include/blsw.h): ONE aggregate signature per instance over K (key, message) pairs with their
+    own messages, e(-g1, sig) * prod_j e(pk_j, H(m_j)) == 1 — every key decoded with its subgroup check and refused when it is the identity, one final
+    exponentiation per instance. uint8 cuda tensors pks48 [n, K, 48], msgs [n, K, msg_len], sig96 [n, 96]; counts: None (every instance uses all K
+    pairs) or an int32 / uint32 cuda tensor [n] — instance i uses its FIRST counts[i] pairs, which is how ragged lists travel padded to the longest.
+    -> int32 [n] verdicts (1 / 0; a count of 0 or beyond K, a key or signature that does not decode and an identity key are false), or a tuple of
+    them followed by what was asked for, in this order: status [n, 2] int32 ([i, 0] of the instance's keys and count, [i, 1] of the signature),
+    key_status [n, K] int32 of every key, used or not. The workspace is allocated per call (the caching allocator keeps it) after check_capacity: its
+    dominant term is 19.6 KB of lines per pair."""
+    torch = _require_cuda()
+    n, K, msg_len = pks48.shape[0], pks48.shape[1], msgs.shape[2]
+    assert pks48.shape == (n, K, 48) and msgs.shape == (n, K, msg_len) and sig96.shape == (n, 96)
+    assert all(t.dtype == torch.uint8 and t.is_contiguous() for t in (pks48, msgs, sig96))
+    dev = pks48.device
+    if counts is not None:
+        assert counts.shape == (n,) and counts.element_size() == 4 and not counts.is_floating_point() and counts.is_contiguous() and counts.device == dev
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_verify_pairs_workspace_bytes(n, msg_len, K, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_verify_pairs_workspace_bytes failed: %d" % rc)
+    check_capacity(dev, "verify_pairs (n = %d, %d pairs)" % (n, K), wb.value)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    res = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    key_status = torch.empty((n, K), dtype=torch.int32, device=dev) if want_key_status else None
+    rc = lib().blsw_verify_pairs_batch(pks48.data_ptr(), msgs.data_ptr() if msg_len else None, msg_len, K, counts.data_ptr() if counts is not None else None, sig96.data_ptr(), n,
+                                       res.data_ptr(), status.data_ptr(), key_status.data_ptr() if want_key_status else None, ws.data_ptr(), ws.numel(),
+                                       torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_verify_pairs_batch failed: %d" % rc)
+    extra = ([status] if want_status else []) + ([key_status] if want_key_status else [])
+    return (res, *extra) if extra else res
 
 
 COMMITTEE_LANES = _header_define("BLSW_COMMITTEE_LANES")  # lanes that share one instance's key sum

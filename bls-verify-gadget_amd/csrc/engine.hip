@@ -1266,21 +1266,21 @@ static int put_desc(StepDesc* d_desc, const StepDesc& h, hipStream_t st) {
 // Prologue of the value-only direct calls (hash to G2, verify, sign) on the device that owns `st` (the caller holds its DeviceGuard): n lanes carved
 // at d_workspace + off_ws, the one-step descriptor (the messages) at the workspace head
 static int direct_values_group(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, void* d_workspace, uint64_t workspace_bytes, uint64_t off_ws, hipStream_t st,
-                               Group* g) {
+                               Group* g, bool latency = true) {
     blsw_layout_t L;
     make_layout(msg_len, &L);
     char* base = reinterpret_cast<char*>(d_workspace);
-    const Workspace ws = carve(base + off_ws, n, L, false, DEFAULT_MODES);
+    const Workspace ws = carve(base + off_ws, n, L, false, DEFAULT_MODES, 0, latency);
     if (off_ws + ws.total_bytes > workspace_bytes) return BLSW_ERR_WORKSPACE;
     StepDesc* d_desc = reinterpret_cast<StepDesc*>(base);
     *g = make_group(1, n, 1, msg_len, d_desc, L, ws);
     StepDesc h = {nullptr, nullptr, d_msg, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
     return put_desc(d_desc, h, st);
 }
-static uint64_t direct_values_bytes(uint64_t n, uint32_t msg_len, uint64_t off_ws) {
+static uint64_t direct_values_bytes(uint64_t n, uint32_t msg_len, uint64_t off_ws, bool latency = true) {
     blsw_layout_t L;
     make_layout(msg_len, &L);
-    return off_ws + carve(nullptr, n, L, false, DEFAULT_MODES).total_bytes;
+    return off_ws + carve(nullptr, n, L, false, DEFAULT_MODES, 0, latency).total_bytes;
 }
 // the value-only hash to G2 of the group's messages, into its workspace
 static void launch_values_hash(const Group& g, hipStream_t st) {
@@ -1393,6 +1393,54 @@ int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, cons
     launch_verify_groups(n, group, BLSW_VGROUP_CHUNK, g.ws, pk_xy, sig_xy, d_status, d_scalars, reinterpret_cast<Fp*>(base + f.p_scaled), reinterpret_cast<Fp*>(base + f.s_scaled),
                          reinterpret_cast<Fp*>(base + f.sum), reinterpret_cast<int32_t*>(base + f.gflag), reinterpret_cast<Fp*>(base + f.lines_h),
                          reinterpret_cast<Fp*>(base + f.lines_g), reinterpret_cast<Fp*>(base + f.partials), d_group_result, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+// One aggregate signature over n_pairs (key, message) pairs per instance (include/blsw.h; vpairs.hpp). Workspace: the step descriptor, the decoded
+// keys and signatures, the keys' statuses (used when the caller passes no d_key_status), one set of lines per pair and per signature, the partial
+// products, then the hash's carve over the n * n_pairs messages.
+struct VerifyPairsOffsets {
+    uint64_t key, sig, key_status, lines_h, lines_s, partials;
+};
+static_assert(BLSW_VPAIRS_CHUNK >= 1 && BLSW_VPAIRS_CHUNK <= 31, "a chunk's pairs and the instance's own are the bits of one 32-bit mask");
+static bool verify_pairs_shape_ok(uint64_t n, uint32_t msg_len, uint32_t n_pairs) {
+    return n != 0 && n_pairs != 0 && n_pairs <= 65535 && n <= 0x7fffffffu && n * n_pairs <= 0x7fffffffu && msg_len <= 65535;
+}
+static uint64_t verify_pairs_offsets(uint64_t n, uint32_t n_pairs, VerifyPairsOffsets* f) {
+    const uint64_t NK = n * n_pairs, teams = n * ((n_pairs + BLSW_VPAIRS_CHUNK - 1) / BLSW_VPAIRS_CHUNK);
+    uint64_t o = 256;  // the step descriptor
+    f->key = o;
+    o = align_up(o + NK * 2 * sizeof(Fp), 256);
+    f->sig = o;
+    o = align_up(o + n * 192, 256);
+    f->key_status = o;
+    o = align_up(o + NK * sizeof(int32_t), 256);
+    f->lines_h = o;
+    o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * NK * sizeof(Fp), 256);
+    f->lines_s = o;
+    o = align_up(o + (uint64_t)BLSW_VLINE_ROWS * n * sizeof(Fp), 256);
+    f->partials = o;
+    return align_up(o + teams * 12 * sizeof(Fp), 256);
+}
+int blsw_verify_pairs_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_pairs, uint64_t* bytes) {
+    if (!bytes || !verify_pairs_shape_ok(n, msg_len, n_pairs)) return BLSW_ERR_ARG;
+    VerifyPairsOffsets f;
+    *bytes = direct_values_bytes(n * n_pairs, msg_len, verify_pairs_offsets(n, n_pairs, &f), false);  // no latency buffers: non-decreasing in n and n_pairs
+    return BLSW_OK;
+}
+int blsw_verify_pairs_batch(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts, const uint8_t* d_sig96, uint64_t n,
+                            int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    if (!verify_pairs_shape_ok(n, msg_len, n_pairs) || !d_pks48 || !d_sig96 || (!d_msgs && msg_len) || !d_result || !d_status || !d_workspace) return BLSW_ERR_ARG;
+    VerifyPairsOffsets f;
+    const uint64_t off_ws = verify_pairs_offsets(n, n_pairs, &f);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    Group g;
+    if (int rc = direct_values_group(d_msgs, msg_len, n * n_pairs, d_workspace, workspace_bytes, off_ws, st, &g, false)) return rc;
+    launch_values_hash(g, st);
+    launch_verify_pairs(n, n_pairs, BLSW_VPAIRS_CHUNK, g.ws, d_pks48, d_sig96, d_counts, reinterpret_cast<Fp*>(base + f.key), reinterpret_cast<uint64_t*>(base + f.sig),
+                        d_key_status ? d_key_status : reinterpret_cast<int32_t*>(base + f.key_status), d_status, reinterpret_cast<Fp*>(base + f.lines_h),
+                        reinterpret_cast<Fp*>(base + f.lines_s), reinterpret_cast<Fp*>(base + f.partials), d_result, st);
     return hip_ok(hipGetLastError(), "launch");
 }
 // One committee, n bitmaps (include/blsw.h; committee.hpp). Workspace: what the chosen verifier's offsets lay out (the step descriptor, pk_xy — here

@@ -150,7 +150,8 @@ inline MultiStaging staging_layout_multi(const blsw_layout_t& L) {
     return m;
 }
 // N lanes of per-(pk, msg) work, n_sig lanes of per-signature work (n_sig = N except for the N+1-pair product)
-inline Workspace carve(void* base, uint64_t N, const blsw_layout_t& L, bool with_staging, const Modes& m, uint64_t n_sig = 0) {
+// latency = false leaves out the buffers of the latency kernels, which the value-only hash never touches: a size that is linear in N
+inline Workspace carve(void* base, uint64_t N, const blsw_layout_t& L, bool with_staging, const Modes& m, uint64_t n_sig = 0, bool latency = true) {
     Workspace w;
     if (n_sig == 0) n_sig = N;
     w.sha_words = align_up((L.sha_bits + 31) / 32 + 1, BLSW_BITS_CHUNK_WORDS);
@@ -169,7 +170,7 @@ inline Workspace carve(void* base, uint64_t N, const blsw_layout_t& L, bool with
     w.coeff_sig = reinterpret_cast<Fp*>(take(272ull * n_sig * sizeof(Fp)));
     w.n_sig = n_sig;
     w.keyproj = L.n_keys && !L.pk_mode ? reinterpret_cast<Fp*>(take(3ull * N * L.n_keys * sizeof(Fp))) : nullptr;
-    const bool small = N <= BLSW_LATENCY_MAX_LANES;  // (not a test of a carved pointer: with base == nullptr the carve only measures)
+    const bool small = latency && N <= BLSW_LATENCY_MAX_LANES;  // (not a test of a carved pointer: with base == nullptr the carve only measures)
     w.cofv = small ? reinterpret_cast<Fp*>(take((uint64_t)BLSW_COFV_ELEMS * N * sizeof(Fp))) : nullptr;
     w.prepv_h = small ? reinterpret_cast<Fp*>(take((uint64_t)BLSW_PREPV_ELEMS * N * sizeof(Fp))) : nullptr;
     w.prepv_sig = small ? reinterpret_cast<Fp*>(take((uint64_t)BLSW_PREPV_ELEMS * n_sig * sizeof(Fp))) : nullptr;
@@ -845,6 +846,10 @@ void launch_verify_values(uint64_t n, const Workspace& ws, const uint64_t* pk_xy
 // (k_vgroups.hip, vgroups.hpp). `chunk` <= 31 pairs per team.
 void launch_verify_groups(uint64_t n, uint32_t group, uint32_t chunk, const Workspace& ws, const uint64_t* pk_xy, const uint64_t* sig_xy, const int32_t* status, const uint64_t* scalars,
                           Fp* p_scaled, Fp* s_scaled, Fp* sum_xy, int32_t* gflag, Fp* lines_h, Fp* lines_g, Fp* partials, int32_t* result, hipStream_t st);
+// blsw_verify_pairs_batch: decode of n * n_pairs keys and n signatures, the instances' statuses, one line chain per used pair and per signature,
+// chunked fold, one final exponentiation per instance (k_vpairs.hip, vpairs.hpp). `chunk` <= 31 pairs per team; ws holds the hash of the n * n_pairs messages.
+void launch_verify_pairs(uint64_t n, uint32_t n_pairs, uint32_t chunk, const Workspace& ws, const uint8_t* pks48, const uint8_t* sig96, const uint32_t* counts, Fp* key_xy,
+                         uint64_t* sig_xy, int32_t* key_status, int32_t* status, Fp* lines_h, Fp* lines_s, Fp* partials, int32_t* result, hipStream_t st);
 // blsw_committee_verify_batch (k_committee.hip, committee.hpp): the committee's keys into `table` [2][n_keys] and key_status together with the n
 // signatures; then per instance the sum of the keys its bitmap row selects -> pk_xy [n][12], status[i][0], count / agg48 (nullable)
 void launch_committee_decode(const uint8_t* pks48, uint32_t n_keys, const uint8_t* sig96, uint64_t n, Fp* table, int32_t* key_status, uint64_t* sig_xy, int32_t* status,

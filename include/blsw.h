@@ -699,6 +699,42 @@ int blsw_verify_groups_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t gr
 int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
                              uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
+/* AggregateVerify of the BLS signature draft as VALUES: ONE aggregate signature over n_pairs (key, message) pairs with their own messages,
+ *     e(-g1, sig) * prod_j e(pk_j, H(msg_j)) == 1
+ * from compressed bytes — the third verification form next to blsw_verify_batch (Verify) and the fast_aggregate_verify entries. New symbols only: the
+ * ABI number stays 17. Every key and the signature are decoded with their subgroup checks, every message is hashed to G2, every used pair gets one
+ * projective line chain (no inversion per step), a six-lane team folds BLSW_VPAIRS_CHUNK pairs with shared squarings, and an instance pays ONE final
+ * exponentiation (csrc/vpairs.hpp). The ciphersuite is the library's one (..._POP_): repeated messages are legal, no distinctness check is made.
+ *   d_pks48 [n][n_pairs][48], d_msgs [n][n_pairs][msg_len], d_sig96 [n][96]
+ *   d_counts [n] uint32 (nullable): instance i uses its FIRST count_i pairs — ragged lists travel padded to the longest; NULL = all n_pairs
+ *   d_key_status [n][n_pairs] int32 (nullable): BLSW_ST_* of every key, used or not
+ *   d_status [n][2] int32: [i][1] the signature's status exactly as blsw_verify_batch writes it; [i][0], in this order:
+ *     1. BLSW_ST_BAD_INDEX if count_i > n_pairs: no verdict depends on anything the instance holds;
+ *     2. else BLSW_ST_IDENTITY if count_i == 0 (the draft requires at least one pair; as the committee form's empty selection);
+ *     3. else the status of the lowest-indexed USED pair whose key is not BLSW_ST_OK — a well-formed identity key is BLSW_ST_IDENTITY here: every
+ *        key goes through KeyValidate, as BLS::verify rejects the identity key, and unlike a summand of PublicKey::aggregate;
+ *     4. else BLSW_ST_OK.
+ *   d_result [n] int32: 1 iff both entries of d_status[i] are BLSW_ST_OK and the product over the used pairs is one. Every error counts as false.
+ * What callers (and the tests) can rest on:
+ *   Q1  n_pairs == 1, d_counts == NULL: d_result and d_status are exactly blsw_verify_batch's.
+ *   Q2  the verdict does not change under a permutation of an instance's used pairs; pairs at j >= count_i have no influence whatever their bytes.
+ *   Q3  all used messages of an instance equal: the verdict of fast_aggregate_verify on the same keys (blsw_aggregate_points_batch(1, ..), then
+ *       blsw_verify_batch) — except for a list with a well-formed identity key, which the aggregate form accepts as a summand and this one refuses.
+ *   Q4  on non-identity points of the prime-order subgroups the verdict is the Boolean of the N+1-pair circuit (blsw_verify_multi_batch).
+ * BLSW_ERR_ARG before any HIP call, nothing written: n == 0, n_pairs == 0 or > 65535, n * n_pairs > 0x7fffffff, msg_len > 65535, a NULL among
+ *   d_pks48, d_sig96, d_result, d_status, d_workspace, or d_msgs == NULL with msg_len != 0. BLSW_ERR_WORKSPACE for a workspace below
+ *   blsw_verify_pairs_workspace_bytes(n, msg_len, n_pairs), which is non-decreasing in each argument. What this entry adds to it is dominated by ONE
+ *   set of lines per pair, BLSW_VLINE_ROWS (6 * 68 field elements) * 48 bytes = 19.6 KB (n * n_pairs = 65 536 pairs: 1.3 GB); the hash's carve that
+ *   every value entry shares stands next to it with 109 KB per message (without the buffers of the latency kernels, which blsw_verify_batch's
+ *   workspace carries up to 4 096 instances): about 130 KB per pair in all, by which callers size their calls.
+ *   Asynchronous on `stream` after the one synchronising descriptor copy the other value entries make. */
+#ifndef BLSW_VPAIRS_CHUNK
+#define BLSW_VPAIRS_CHUNK 8 /* pairs one six-lane team folds with shared squarings (<= 31). Measured at K = 128, n = 512 (65 536 pairs; profiles/pairs_rate.txt): 2 -> 61.6, 4 -> 54.9, 8 -> 51.3, 16 -> 64.4, 31 -> 87.4 ms: from 16 on the call has fewer teams (4 096) than the device holds at once (10 240) */
+#endif
+int blsw_verify_pairs_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_pairs, uint64_t* bytes);
+int blsw_verify_pairs_batch(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts, const uint8_t* d_sig96,
+                            uint64_t n, int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
 /* fast_aggregate_verify (tests/tests.rs:296-334) as VALUES over ONE committee and many bitmaps, the shape of a sync-committee verifier: K keys
  * given once, and per instance a participation bitmap, one message and one aggregate signature. New symbols only: the ABI number stays 17. The
  * committee is decoded ONCE per call (K subgroup checks, not n * K), every instance sums its selected keys with BLSW_COMMITTEE_LANES lanes (a

@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -1182,6 +1183,64 @@ struct BLS {
         }
         const std::vector<bool> r = fast_aggregate_verify_indexed(params, registry, l2, m2, s2);
         for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
+        return out;
+    }
+    // AggregateVerify of the signature draft as values (blsw_verify_pairs_batch, include/blsw.h): instance i is ONE aggregate signature over the pairs
+    // (key_lists[i][j], message_lists[i][j]) with their own messages. The lists may be ragged: they travel padded to the longest with their counts.
+    // True iff the list is not empty, every key decodes to a non-identity point of the subgroup (an identity key is refused, unlike a summand of
+    // fast_aggregate_verify), the signature decodes and e(-g1, sig) * prod_j e(pk_j, H(m_j)) == 1. All messages of a batch have one length.
+    // status [n][2] (the instance's keys and count, the signature) and key_status [n][longest] (every key, the padding included) are filled when given.
+    static std::vector<bool> aggregate_verify(const Parameters&, const std::vector<std::vector<PublicKey>>& key_lists,
+                                              const std::vector<std::vector<std::vector<uint8_t>>>& message_lists, const std::vector<Signature>& sigs,
+                                              std::vector<int32_t>* status = nullptr, std::vector<int32_t>* key_status = nullptr) {
+        const size_t n = key_lists.size();
+        if (n == 0 || message_lists.size() != n || sigs.size() != n) throw Error("BLS::aggregate_verify: one key list, message list and signature per instance", BLSW_ERR_ARG);
+        size_t K = 1, msg_len = 0;
+        bool have_len = false;
+        for (size_t i = 0; i < n; i++) {
+            if (message_lists[i].size() != key_lists[i].size()) throw Error("BLS::aggregate_verify: one message per key", BLSW_ERR_ARG);
+            K = std::max(K, key_lists[i].size());
+            for (const std::vector<uint8_t>& m : message_lists[i]) {
+                if (have_len && m.size() != msg_len) throw Error("BLS::aggregate_verify: messages of one length per batch", BLSW_ERR_ARG);
+                msg_len = m.size();
+                have_len = true;
+            }
+        }
+        if (K > 65535) throw Error("BLS::aggregate_verify: at most 65535 pairs per instance", BLSW_ERR_ARG);
+        std::vector<uint8_t> pk(n * K * 48, 0), msg(n * K * msg_len, 0), sg(n * 96);
+        std::vector<uint32_t> counts(n);
+        for (size_t i = 0; i < n; i++) {
+            counts[i] = (uint32_t)key_lists[i].size();
+            for (size_t j = 0; j < key_lists[i].size(); j++) {
+                std::memcpy(&pk[48 * (i * K + j)], key_lists[i][j].bytes.data(), 48);
+                if (msg_len) std::memcpy(&msg[msg_len * (i * K + j)], message_lists[i][j].data(), msg_len);
+            }
+            std::memcpy(&sg[96 * i], sigs[i].bytes.data(), 96);
+        }
+        uint64_t bytes = 0;
+        check(blsw_verify_pairs_workspace_bytes(n, (uint32_t)msg_len, (uint32_t)K, &bytes), "blsw_verify_pairs_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_pk(pk.size()), d_msg(msg.size()), d_sg(sg.size()), d_cnt(n * 4), d_st(n * 8), d_kst(n * K * 4), d_res(n * 4);
+        d_pk.upload(pk.data(), pk.size());
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        d_sg.upload(sg.data(), sg.size());
+        d_cnt.upload(counts.data(), n * 4);
+        check(blsw_verify_pairs_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_msg.get()), (uint32_t)msg_len, (uint32_t)K,
+                                      static_cast<const uint32_t*>(d_cnt.get()), static_cast<const uint8_t*>(d_sg.get()), n, static_cast<int32_t*>(d_res.get()),
+                                      static_cast<int32_t*>(d_st.get()), static_cast<int32_t*>(d_kst.get()), ws.get(), bytes, nullptr),
+              "blsw_verify_pairs_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n);
+        d_res.download(r.data(), n * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
+        }
+        if (key_status) {
+            key_status->resize(n * K);
+            d_kst.download(key_status->data(), n * K * 4);
+        }
+        std::vector<bool> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = r[i] == 1;
         return out;
     }
 };
