@@ -61,6 +61,10 @@ COMPACT_INST = 3  # compact_locate_multi: an instance tile (COMPACT_TILE: a pair
 ERR_BUSY = 6
 
 
+class blsw_dst_t(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_uint8 * 255), ("len", ctypes.c_uint8)]
+
+
 class BlswError(RuntimeError):
     pass
 
@@ -199,8 +203,22 @@ def lib():
         L.blsw_r1cs_check_compact_multi.argtypes = [vp, cm, vp, vp, u64, vp, vp, vp]
         L.blsw_r1cs_check_compact_multi_ex.argtypes = [vp, cm, vp, vp, u64, u32, vp, vp, vp]
         L.blsw_r1cs_evaluate_compact_multi.argtypes = [vp, cm, vp, vp, u64, u64, u64, vp, vp, vp, vp]
+        dp = ctypes.POINTER(blsw_dst_t)
+        L.blsw_dst_set.argtypes = [dp, vp, u32]
+        L.blsw_dst_default.argtypes = [dp]
+        L.blsw_dst_pop.argtypes = [dp]
+        L.blsw_hash_to_field_batch.argtypes = [vp, u32, u64, dp, vp, vp]
+        for name in _DST_ENTRIES:  # the plain entry's arguments with the tag in front of the stream
+            plain = getattr(L, name).argtypes
+            getattr(L, name + "_dst").argtypes = list(plain[:-1]) + [dp, plain[-1]]
+        L.blsw_pop_prove_batch.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp]
+        L.blsw_pop_verify_batch.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp]
         _lib = L
     return _lib
+
+
+_DST_ENTRIES = ["blsw_hash_to_g2_batch", "blsw_sign_batch", "blsw_verify_batch", "blsw_verify_groups_batch", "blsw_verify_pairs_batch", "blsw_committee_verify_batch",
+                "blsw_registry_verify_batch"]
 
 
 EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default", "blsw_engine_workspace_bytes", "blsw_engine_workspace_bytes_ex", "blsw_engine_create",
@@ -220,7 +238,29 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_compact_layout_multi", "blsw_compact_locate_multi", "blsw_compact_locate_multi_range", "blsw_r1cs_pair_families",
                     "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi",
                     "blsw_registry_bytes", "blsw_registry_create", "blsw_registry_append", "blsw_registry_size", "blsw_registry_key_status", "blsw_registry_destroy",
-                    "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch", "blsw_verify_pairs_workspace_bytes", "blsw_verify_pairs_batch"]
+                    "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch", "blsw_verify_pairs_workspace_bytes", "blsw_verify_pairs_batch",
+                    "blsw_dst_set", "blsw_dst_default", "blsw_dst_pop", "blsw_hash_to_field_batch", "blsw_pop_prove_batch", "blsw_pop_verify_batch"] + [e + "_dst" for e in _DST_ENTRIES]
+
+DST_DEFAULT = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # the library's tag: what every value entry hashes under with dst=None
+DST_POP = b"BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # PopProve / PopVerify of the signature draft
+
+
+def _dst_struct(dst):
+    """bytes of 1 .. 255 -> blsw_dst_t (blsw_dst_set states the rule)"""
+    t = blsw_dst_t()
+    raw = bytes(dst)
+    rc = lib().blsw_dst_set(ctypes.byref(t), raw, len(raw))
+    if rc:
+        raise BlswError("blsw_dst_set failed: %d (a tag has 1 .. 255 bytes, this one %d)" % (rc, len(raw)))
+    return t
+
+
+def _dst_entry(name, dst):
+    """the C entry `name` for dst=None — the call is then exactly what it was — or its _dst form with the tag bound in front of the stream"""
+    if dst is None:
+        return getattr(lib(), name)
+    fn, t = getattr(lib(), name + "_dst"), _dst_struct(dst)
+    return lambda *a: fn(*a[:-1], ctypes.byref(t), a[-1])
 
 
 PARAMS_MODES = {"constant": 0, "witness": 1}
@@ -999,10 +1039,12 @@ def aggregate_public_keys(pk48):
 _VERIFY_WS = {}
 
 
-def verify_batch(pk48, msg, sig96, want_status=False):
+def verify_batch(pk48, msg, sig96, want_status=False, dst=None):
     """BLS::verify (bls.rs:427-458) for a batch as VALUES (blsw_verify_batch: the native algorithm — decode with subgroup checks, hash to G2, a two-pair
     Miller loop over projective lines, final exponentiation — no circuit): uint8 cuda tensors pk48 [n, 48], msg [n, msg_len], sig96 [n, 96] ->
-    int32 [n] verdicts (1 / 0; every Err of the reference's verify counts as false), optionally with the decode statuses [n, 2]."""
+    int32 [n] verdicts (1 / 0; every Err of the reference's verify counts as false), optionally with the decode statuses [n, 2].
+    dst (here and on every value function that takes it): None = the library's tag DST_DEFAULT through the plain entry; bytes of 1 .. 255 = the
+    domain separation tag of hash_to_curve, through the entry's _dst form (include/blsw.h) — the same workspace, another hash kernel."""
     torch = _require_cuda()
     n, msg_len = pk48.shape[0], msg.shape[1]
     assert pk48.shape == (n, 48) and sig96.shape == (n, 96) and msg.shape[0] == n and pk48.is_contiguous() and sig96.is_contiguous() and msg.is_contiguous()
@@ -1018,7 +1060,7 @@ def verify_batch(pk48, msg, sig96, want_status=False):
         ws = _VERIFY_WS[key] = torch.empty(wb.value, dtype=torch.uint8, device=dev)
     res = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    rc = lib().blsw_verify_batch(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n, res.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+    rc = _dst_entry("blsw_verify_batch", dst)(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n, res.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                  torch.cuda.current_stream(dev).cuda_stream)
     if rc:
         raise BlswError("blsw_verify_batch failed: %d" % rc)
@@ -1047,7 +1089,7 @@ def _group_scalars(torch, n, dev):
     return torch.from_numpy(r.view(np.int64)).to(dev)
 
 
-def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False):
+def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
     """Batch verification of GROUPS of triples with random coefficients (blsw_verify_groups_batch, include/blsw.h): group j is instances
     [j * group, min(n, (j + 1) * group)) and its verdict is 1 iff every instance decodes (both statuses OK), every coefficient is non-zero and
     prod_i e(r_i pk_i, H(m_i)) * e(-g1, sum_i r_i sig_i) == 1 — one final exponentiation per group instead of one per triple. uint8 cuda tensors as
@@ -1068,31 +1110,31 @@ def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False):
     ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
     res = torch.empty((n + group - 1) // group, dtype=torch.int32, device=dev)
     status = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    rc = lib().blsw_verify_groups_batch(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n, scalars.data_ptr(), group, res.data_ptr(),
+    rc = _dst_entry("blsw_verify_groups_batch", dst)(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n, scalars.data_ptr(), group, res.data_ptr(),
                                         status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
     if rc:
         raise BlswError("blsw_verify_groups_batch failed: %d" % rc)
     return (res, status) if want_status else res
 
 
-def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=False):
+def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
     """verify_batch through verify_groups: int32 [n] with the meaning of verify_batch. The instances of passing groups are 1; the instances of failing
     groups are gathered, put through verify_batch and scattered back. ONE host synchronisation, to learn which groups failed. A batch in which most
     groups hold a bad instance is slower this way than verify_batch: it pays for the groups and then for nearly the whole batch again."""
     torch = _require_cuda()
     n = pk48.shape[0]
-    gres, status = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True)
+    gres, status = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
     res = gres.repeat_interleave(group)[:n].contiguous()
     bad = torch.nonzero(res == 0).flatten()  # the synchronisation
     if bad.numel():
-        res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous())
+        res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous(), dst=dst)
     return (res, status) if want_status else res
 
 
 VERIFY_PAIRS_CHUNK = _header_define("BLSW_VPAIRS_CHUNK")  # pairs of one instance that one six-lane team folds with shared squarings
 
 
-def verify_pairs(pks48, msgs, sig96, counts=None, want_status=False, want_key_status=False):
+def verify_pairs(pks48, msgs, sig96, counts=None, want_status=False, want_key_status=False, dst=None):
     """AggregateVerify as values (blsw_verify_pairs_batch, include/blsw.h): ONE aggregate signature per instance over K (key, message) pairs with their
     own messages, e(-g1, sig) * prod_j e(pk_j, H(m_j)) == 1 — every key decoded with its subgroup check and refused when it is the identity, one final
     exponentiation per instance. uint8 cuda tensors pks48 [n, K, 48], msgs [n, K, msg_len], sig96 [n, 96]; counts: None (every instance uses all K
@@ -1117,7 +1159,7 @@ def verify_pairs(pks48, msgs, sig96, counts=None, want_status=False, want_key_st
     res = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty((n, 2), dtype=torch.int32, device=dev)
     key_status = torch.empty((n, K), dtype=torch.int32, device=dev) if want_key_status else None
-    rc = lib().blsw_verify_pairs_batch(pks48.data_ptr(), msgs.data_ptr() if msg_len else None, msg_len, K, counts.data_ptr() if counts is not None else None, sig96.data_ptr(), n,
+    rc = _dst_entry("blsw_verify_pairs_batch", dst)(pks48.data_ptr(), msgs.data_ptr() if msg_len else None, msg_len, K, counts.data_ptr() if counts is not None else None, sig96.data_ptr(), n,
                                        res.data_ptr(), status.data_ptr(), key_status.data_ptr() if want_key_status else None, ws.data_ptr(), ws.numel(),
                                        torch.cuda.current_stream(dev).cuda_stream)
     if rc:
@@ -1129,7 +1171,7 @@ def verify_pairs(pks48, msgs, sig96, counts=None, want_status=False, want_key_st
 COMMITTEE_LANES = _header_define("BLSW_COMMITTEE_LANES")  # lanes that share one instance's key sum
 
 
-def committee_verify(pks48, bitmap, msg, sig96, group=0, scalars=None, want_status=False, want_count=False, want_aggregate=False):
+def committee_verify(pks48, bitmap, msg, sig96, group=0, scalars=None, want_status=False, want_count=False, want_aggregate=False, dst=None):
     """fast_aggregate_verify as values over ONE committee and n bitmaps (blsw_committee_verify_batch, include/blsw.h): uint8 cuda tensors pks48
     [K, 48] (the committee, given once), bitmap [n, K] (a non-zero byte selects the key), msg [n, msg_len], sig96 [n, 96]. The committee is decoded
     once per call and every instance sums its selected keys with COMMITTEE_LANES lanes.
@@ -1158,7 +1200,7 @@ def committee_verify(pks48, bitmap, msg, sig96, group=0, scalars=None, want_stat
     key_status = torch.empty(K, dtype=torch.int32, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev) if want_count else None
     agg = torch.empty((n, 48), dtype=torch.uint8, device=dev) if want_aggregate else None
-    rc = lib().blsw_committee_verify_batch(pks48.data_ptr(), K, bitmap.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n,
+    rc = _dst_entry("blsw_committee_verify_batch", dst)(pks48.data_ptr(), K, bitmap.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n,
                                            scalars.data_ptr() if scalars is not None else None, group, res.data_ptr(), count.data_ptr() if want_count else None,
                                            status.data_ptr(), key_status.data_ptr(), agg.data_ptr() if want_aggregate else None, ws.data_ptr(), ws.numel(),
                                            torch.cuda.current_stream(dev).cuda_stream)
@@ -1168,17 +1210,17 @@ def committee_verify(pks48, bitmap, msg, sig96, group=0, scalars=None, want_stat
     return (res, *extra) if extra else res
 
 
-def committee_verify_grouped(pks48, bitmap, msg, sig96, group=64, scalars=None, want_status=False):
+def committee_verify_grouped(pks48, bitmap, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
     """committee_verify(group=0)'s per-instance verdicts through the grouped form: the instances of passing groups are 1; the instances of failing
     groups are gathered, put through committee_verify(group=0) and scattered back. ONE host synchronisation, to learn which groups failed, like
     verify_batch_grouped — and like it slower than the plain call when most groups hold a bad instance."""
     torch = _require_cuda()
     n = bitmap.shape[0]
-    gres, st = committee_verify(pks48, bitmap, msg, sig96, group=group, scalars=scalars, want_status=True)
+    gres, st = committee_verify(pks48, bitmap, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
     res = gres.repeat_interleave(group)[:n].contiguous()
     bad = torch.nonzero(res == 0).flatten()  # the synchronisation
     if bad.numel():
-        res[bad] = committee_verify(pks48, bitmap[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous())
+        res[bad] = committee_verify(pks48, bitmap[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous(), dst=dst)
     return (res, st) if want_status else res
 
 
@@ -1247,7 +1289,7 @@ class KeyRegistry:
             pass
 
 
-def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=None, want_status=False, want_aggregate=False):
+def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=None, want_status=False, want_aggregate=False, dst=None):
     """fast_aggregate_verify as values over a KeyRegistry and n index lists (blsw_registry_verify_batch, include/blsw.h): set i is
     indices[offsets[i]:offsets[i + 1]] — indices a cuda tensor [n_indices] of 32-bit integers (int32 storage of the uint32 indices), offsets [n + 1]
     of 64-bit integers; uint8 cuda tensors msg [n, msg_len], sig96 [n, 96]. A repeated index is added as often as it occurs.
@@ -1273,7 +1315,7 @@ def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=Non
     res = torch.empty((n + group - 1) // group if group else n, dtype=torch.int32, device=dev)
     status = torch.empty((n, 2), dtype=torch.int32, device=dev)
     agg = torch.empty((n, 48), dtype=torch.uint8, device=dev) if want_aggregate else None
-    rc = lib().blsw_registry_verify_batch(registry._r, indices.data_ptr() if n_indices else None, n_indices, offsets.data_ptr(), sig96.data_ptr(),
+    rc = _dst_entry("blsw_registry_verify_batch", dst)(registry._r, indices.data_ptr() if n_indices else None, n_indices, offsets.data_ptr(), sig96.data_ptr(),
                                           msg.data_ptr() if msg_len else None, msg_len, n, scalars.data_ptr() if scalars is not None else None, group, res.data_ptr(),
                                           status.data_ptr(), agg.data_ptr() if want_aggregate else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
     if rc:
@@ -1282,7 +1324,7 @@ def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=Non
     return (res, *extra) if extra else res
 
 
-def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, scalars=None, want_status=False):
+def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
     """registry_verify(group=0)'s per-set verdicts through the grouped form: the sets of passing groups are 1; the sets of failing groups are
     re-checked with the per-set form and scattered back. CSR is one run of n + 1 offsets and the failing sets' lists are not adjacent, so their
     entries are gathered into an index list of their own. ONE host synchronisation: the group verdicts and the n + 1 offsets come to the host in a
@@ -1292,7 +1334,7 @@ def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, sc
     import numpy as np
 
     n, dev = msg.shape[0], msg.device
-    gres, st = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True)
+    gres, st = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
     res = gres.repeat_interleave(group)[:n].contiguous()
     host = torch.cat([res.to(torch.int64), offsets.view(torch.int64)]).cpu().numpy()  # the synchronisation
     bad = np.flatnonzero(host[:n] == 0)
@@ -1307,7 +1349,7 @@ def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, sc
         sub_idx = indices[torch.from_numpy(pos).to(dev)].contiguous()
         sub_off = torch.from_numpy(np.concatenate([np.zeros(1, np.int64), ends])).to(dev)
         bad_t = torch.from_numpy(bad).to(dev)
-        res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg[bad_t].contiguous(), sig96[bad_t].contiguous())
+        res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg[bad_t].contiguous(), sig96[bad_t].contiguous(), dst=dst)
     return (res, st) if want_status else res
 
 
@@ -1889,7 +1931,7 @@ def fill_rate(tensor, reps=2):
     return v.value
 
 
-def hash_to_g2_batch(message, out=None):
+def hash_to_g2_batch(message, out=None, dst=None):
     """Batched hash_to_g2_with_cons values (hasher.rs:727-740): message [n, msg_len] uint8 cuda tensor -> [n, 24] int64 affine."""
     torch = _require_cuda()
     n, msg_len = message.shape
@@ -1898,7 +1940,7 @@ def hash_to_g2_batch(message, out=None):
     ws = torch.empty(wb.value, dtype=torch.uint8, device=message.device)
     if out is None:
         out = torch.empty((n, 24), dtype=torch.int64, device=message.device)
-    rc = lib().blsw_hash_to_g2_batch(message.data_ptr(), msg_len, n, out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(message.device).cuda_stream)
+    rc = _dst_entry("blsw_hash_to_g2_batch", dst)(message.data_ptr(), msg_len, n, out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(message.device).cuda_stream)
     if rc:
         raise BlswError("blsw_hash_to_g2_batch failed: %d" % rc)
     return out
@@ -1907,7 +1949,7 @@ def hash_to_g2_batch(message, out=None):
 ST_INVALID_SECRET_KEY = 5
 
 
-def sign_batch(sk32_le, message, want_bytes=True):
+def sign_batch(sk32_le, message, want_bytes=True, dst=None):
     """BLS::sign + PublicKey::from(&sk) for a batch (bls.rs:411-425, 183-195): sk32_le [n, 32] uint8 (little-endian Fr, as
     PrivateKey::try_from takes it), message [n, msg_len] uint8, cuda tensors.
     Returns dict(sig96, pk48 (uint8, None unless want_bytes), sig_xy [n,24], pk_xy [n,12] int64 Montgomery, status [n] int32)."""
@@ -1923,10 +1965,68 @@ def sign_batch(sk32_le, message, want_bytes=True):
     sig_xy = torch.empty((n, 24), dtype=torch.int64, device=dev)
     pk_xy = torch.empty((n, 12), dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    rc = lib().blsw_sign_batch(sk32_le.data_ptr(), message.data_ptr(), msg_len, n, sig96.data_ptr() if want_bytes else None, sig_xy.data_ptr(),
+    rc = _dst_entry("blsw_sign_batch", dst)(sk32_le.data_ptr(), message.data_ptr(), msg_len, n, sig96.data_ptr() if want_bytes else None, sig_xy.data_ptr(),
                                pk48.data_ptr() if want_bytes else None, pk_xy.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                torch.cuda.current_stream(dev).cuda_stream)
     if rc:
         raise BlswError("blsw_sign_batch failed: %d" % rc)
     torch.cuda.synchronize(dev)
     return {"sig96": sig96, "pk48": pk48, "sig_xy": sig_xy, "pk_xy": pk_xy, "status": status}
+
+
+def hash_to_field_batch(message, dst=None):
+    """hash_to_field of RFC 9380 for G2 on its own (blsw_hash_to_field_batch): message [n, msg_len] uint8 cuda tensor -> [n, 4, 6] int64 Montgomery
+    (u0.c0, u0.c1, u1.c0, u1.c1) under the tag dst (None = DST_DEFAULT). No workspace."""
+    torch = _require_cuda()
+    n, msg_len = message.shape
+    assert message.dtype == torch.uint8 and message.is_contiguous()
+    out = torch.empty((n, 4, 6), dtype=torch.int64, device=message.device)
+    t = _dst_struct(dst) if dst is not None else None
+    rc = lib().blsw_hash_to_field_batch(message.data_ptr() if msg_len else None, msg_len, n, ctypes.byref(t) if t is not None else None, out.data_ptr(),
+                                        torch.cuda.current_stream(message.device).cuda_stream)
+    if rc:
+        raise BlswError("blsw_hash_to_field_batch failed: %d" % rc)
+    return out
+
+
+def pop_prove(sk32_le):
+    """PopProve of the signature draft's POP ciphersuite for a batch (blsw_pop_prove_batch): sk32_le [n, 32] uint8 cuda tensor (little-endian Fr) ->
+    dict(pk48 [n, 48], proof96 [n, 96] uint8, status [n] int32 as sign_batch's): proof = sk * hash_to_g2(pk48, DST_POP)."""
+    torch = _require_cuda()
+    n = sk32_le.shape[0]
+    assert sk32_le.shape == (n, 32) and sk32_le.dtype == torch.uint8 and sk32_le.is_contiguous()
+    dev = sk32_le.device
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_hash_to_g2_workspace_bytes(n, 48, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_hash_to_g2_workspace_bytes failed: %d" % rc)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    proof96 = torch.empty((n, 96), dtype=torch.uint8, device=dev)
+    pk48 = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib().blsw_pop_prove_batch(sk32_le.data_ptr(), n, proof96.data_ptr(), pk48.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_pop_prove_batch failed: %d" % rc)
+    torch.cuda.synchronize(dev)
+    return {"pk48": pk48, "proof96": proof96, "status": status}
+
+
+def pop_verify(pk48, proof96, want_status=False):
+    """PopVerify for a batch (blsw_pop_verify_batch): uint8 cuda tensors pk48 [n, 48], proof96 [n, 96] -> int32 [n] verdicts — verify_batch with the
+    key's own bytes as the message under DST_POP, KeyValidate included —, optionally with the decode statuses [n, 2] (key, proof)."""
+    torch = _require_cuda()
+    n = pk48.shape[0]
+    assert pk48.shape == (n, 48) and proof96.shape == (n, 96) and pk48.is_contiguous() and proof96.is_contiguous()
+    dev = pk48.device
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_verify_workspace_bytes(n, 48, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_verify_workspace_bytes failed: %d" % rc)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    res = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    rc = lib().blsw_pop_verify_batch(pk48.data_ptr(), proof96.data_ptr(), n, res.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_pop_verify_batch failed: %d" % rc)
+    return (res, status) if want_status else res

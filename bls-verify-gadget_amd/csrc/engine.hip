@@ -1283,23 +1283,35 @@ static uint64_t direct_values_bytes(uint64_t n, uint32_t msg_len, uint64_t off_w
     return off_ws + carve(nullptr, n, L, false, DEFAULT_MODES, 0, latency).total_bytes;
 }
 // the value-only hash to G2 of the group's messages, into its workspace
-static void launch_values_hash(const Group& g, hipStream_t st) {
+// dst: nullptr = the library's tag, compiled into k_sha_values; a caller's tag (checked: dst_ok) travels as the argument of k_sha_values_dst
+static bool dst_ok(const blsw_dst_t* dst) { return !dst || dst->len != 0; }
+static void launch_values_hash(const Group& g, hipStream_t st, const blsw_dst_t* dst = nullptr) {
     const unsigned g1 = (unsigned)((g.N + 63) / 64), g2 = (unsigned)((2 * g.N + 63) / 64);
-    hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
+    if (dst) {
+        DstArg a;
+        dst_arg_build(&a, dst->bytes, dst->len, g.msg_len);
+        hipLaunchKernelGGL(k_sha_values_dst, dim3(g1), dim3(64), 0, st, g, a, (const uint8_t*)nullptr, (Fp*)nullptr);
+    } else {
+        hipLaunchKernelGGL(k_sha_values, dim3(g1), dim3(64), 0, st, g);
+    }
     hipLaunchKernelGGL(k_map_values, dim3(g2), dim3(64), 0, st, g);
     hipLaunchKernelGGL(k_cofactor_values, dim3(g1), dim3(64), 0, st, g);
 }
 
-int blsw_hash_to_g2_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
-                          void* stream_) {
-    if ((!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_out_affine || msg_len > 65535) return BLSW_ERR_ARG;
+int blsw_hash_to_g2_batch_dst(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
+                              const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_out_affine || msg_len > 65535) return BLSW_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
     Group g;
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, 256, st, &g)) return rc;
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     hipLaunchKernelGGL(k_h_to_affine, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, g.ws, d_out_affine);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_hash_to_g2_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
+                          void* stream_) {
+    return blsw_hash_to_g2_batch_dst(d_msg, msg_len, n, d_out_affine, d_workspace, workspace_bytes, nullptr, stream_);
 }
 // BLS::verify (bls.rs:427-458) for a batch of compressed (pk, sig) and messages, as VALUES (no circuit): decode with the endomorphism subgroup checks,
 // the value-only hash to G2, projective line coefficients and a two-pair Miller loop + final exponentiation on the six-lane team (vpairing.hpp).
@@ -1322,9 +1334,9 @@ int blsw_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes) {
     *bytes = direct_values_bytes(n, msg_len, verify_offsets(n, &a, &b, &c, &d));
     return BLSW_OK;
 }
-int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result, int32_t* d_status,
-                      void* d_workspace, uint64_t workspace_bytes, void* stream_) {
-    if (!d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_result || !d_status || !d_workspace || msg_len > 65535) return BLSW_ERR_ARG;
+int blsw_verify_batch_dst(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result, int32_t* d_status,
+                          void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_result || !d_status || !d_workspace || msg_len > 65535) return BLSW_ERR_ARG;
     uint64_t off_pk, off_sig, off_ls, off_lh;
     const uint64_t off_ws = verify_offsets(n, &off_pk, &off_sig, &off_ls, &off_lh);
     char* base = reinterpret_cast<char*>(d_workspace);
@@ -1335,9 +1347,13 @@ int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8
     Group g;
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
     hipLaunchKernelGGL(k_decode, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, d_pk48, d_sig96, n, pk_xy, sig_xy, d_status);
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + off_ls), reinterpret_cast<Fp*>(base + off_lh), d_status, d_result, st);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_verify_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result, int32_t* d_status,
+                      void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    return blsw_verify_batch_dst(d_pk48, d_sig96, d_msg, msg_len, n, d_result, d_status, d_workspace, workspace_bytes, nullptr, stream_);
 }
 // Groups of triples verified with the caller's coefficients (include/blsw.h, ABI 17; vgroups.hpp). Workspace: the step descriptor, the decoded points,
 // the scaled points, the group sums and flags, ONE set of per-instance lines, the per-group lines, the partial products, then the hash's carve.
@@ -1374,9 +1390,9 @@ int blsw_verify_groups_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t gr
     *bytes = direct_values_bytes(n, msg_len, verify_groups_offsets(n, group, &f));
     return BLSW_OK;
 }
-int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
-                             uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
-    if (!d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_scalars || group == 0 || group > 65535 || !d_group_result || !d_status ||
+int blsw_verify_groups_batch_dst(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
+                                 uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !d_pk48 || !d_sig96 || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_scalars || group == 0 || group > 65535 || !d_group_result || !d_status ||
         !d_workspace || msg_len > 65535)
         return BLSW_ERR_ARG;
     VerifyGroupsOffsets f;
@@ -1389,11 +1405,15 @@ int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, cons
     Group g;
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
     hipLaunchKernelGGL(k_decode, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, d_pk48, d_sig96, n, pk_xy, sig_xy, d_status);
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     launch_verify_groups(n, group, BLSW_VGROUP_CHUNK, g.ws, pk_xy, sig_xy, d_status, d_scalars, reinterpret_cast<Fp*>(base + f.p_scaled), reinterpret_cast<Fp*>(base + f.s_scaled),
                          reinterpret_cast<Fp*>(base + f.sum), reinterpret_cast<int32_t*>(base + f.gflag), reinterpret_cast<Fp*>(base + f.lines_h),
                          reinterpret_cast<Fp*>(base + f.lines_g), reinterpret_cast<Fp*>(base + f.partials), d_group_result, st);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_verify_groups_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
+                             uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    return blsw_verify_groups_batch_dst(d_pk48, d_sig96, d_msg, msg_len, n, d_scalars, group, d_group_result, d_status, d_workspace, workspace_bytes, nullptr, stream_);
 }
 // One aggregate signature over n_pairs (key, message) pairs per instance (include/blsw.h; vpairs.hpp). Workspace: the step descriptor, the decoded
 // keys and signatures, the keys' statuses (used when the caller passes no d_key_status), one set of lines per pair and per signature, the partial
@@ -1427,9 +1447,9 @@ int blsw_verify_pairs_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_p
     *bytes = direct_values_bytes(n * n_pairs, msg_len, verify_pairs_offsets(n, n_pairs, &f), false);  // no latency buffers: non-decreasing in n and n_pairs
     return BLSW_OK;
 }
-int blsw_verify_pairs_batch(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts, const uint8_t* d_sig96, uint64_t n,
-                            int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
-    if (!verify_pairs_shape_ok(n, msg_len, n_pairs) || !d_pks48 || !d_sig96 || (!d_msgs && msg_len) || !d_result || !d_status || !d_workspace) return BLSW_ERR_ARG;
+int blsw_verify_pairs_batch_dst(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts, const uint8_t* d_sig96, uint64_t n,
+                                int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !verify_pairs_shape_ok(n, msg_len, n_pairs) || !d_pks48 || !d_sig96 || (!d_msgs && msg_len) || !d_result || !d_status || !d_workspace) return BLSW_ERR_ARG;
     VerifyPairsOffsets f;
     const uint64_t off_ws = verify_pairs_offsets(n, n_pairs, &f);
     char* base = reinterpret_cast<char*>(d_workspace);
@@ -1437,11 +1457,15 @@ int blsw_verify_pairs_batch(const uint8_t* d_pks48, const uint8_t* d_msgs, uint3
     DeviceGuard guard(stream_device(st));
     Group g;
     if (int rc = direct_values_group(d_msgs, msg_len, n * n_pairs, d_workspace, workspace_bytes, off_ws, st, &g, false)) return rc;
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     launch_verify_pairs(n, n_pairs, BLSW_VPAIRS_CHUNK, g.ws, d_pks48, d_sig96, d_counts, reinterpret_cast<Fp*>(base + f.key), reinterpret_cast<uint64_t*>(base + f.sig),
                         d_key_status ? d_key_status : reinterpret_cast<int32_t*>(base + f.key_status), d_status, reinterpret_cast<Fp*>(base + f.lines_h),
                         reinterpret_cast<Fp*>(base + f.lines_s), reinterpret_cast<Fp*>(base + f.partials), d_result, st);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_verify_pairs_batch(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts, const uint8_t* d_sig96, uint64_t n,
+                            int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    return blsw_verify_pairs_batch_dst(d_pks48, d_msgs, msg_len, n_pairs, d_counts, d_sig96, n, d_result, d_status, d_key_status, d_workspace, workspace_bytes, nullptr, stream_);
 }
 // One committee, n bitmaps (include/blsw.h; committee.hpp). Workspace: what the chosen verifier's offsets lay out (the step descriptor, pk_xy — here
 // the aggregated keys — sig_xy, its lines ...), then the decoded committee [2][n_keys], then the hash's carve. The keys' statuses live in the
@@ -1472,10 +1496,10 @@ int blsw_committee_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t
     *bytes = direct_values_bytes(n, msg_len, committee_offsets(n, n_keys, group, &f));
     return BLSW_OK;
 }
-int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const uint8_t* d_bitmap, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n,
-                                const uint64_t* d_scalars, uint32_t group, int32_t* d_result, uint32_t* d_count, int32_t* d_status, int32_t* d_key_status, uint8_t* d_agg48,
-                                void* d_workspace, uint64_t workspace_bytes, void* stream_) {
-    if (!committee_shape_ok(n, msg_len, n_keys, group) || !d_pks48 || !d_bitmap || !d_sig96 || (!d_msg && msg_len) || !d_result || !d_status || !d_key_status || !d_workspace ||
+int blsw_committee_verify_batch_dst(const uint8_t* d_pks48, uint32_t n_keys, const uint8_t* d_bitmap, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n,
+                                    const uint64_t* d_scalars, uint32_t group, int32_t* d_result, uint32_t* d_count, int32_t* d_status, int32_t* d_key_status, uint8_t* d_agg48,
+                                    void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !committee_shape_ok(n, msg_len, n_keys, group) || !d_pks48 || !d_bitmap || !d_sig96 || (!d_msg && msg_len) || !d_result || !d_status || !d_key_status || !d_workspace ||
         (group == 0 ? d_scalars != nullptr : d_scalars == nullptr))
         return BLSW_ERR_ARG;
     CommitteeOffsets f;
@@ -1490,7 +1514,7 @@ int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const u
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
     launch_committee_decode(d_pks48, n_keys, d_sig96, n, table, d_key_status, sig_xy, d_status, st);
     launch_committee_sum(d_bitmap, n_keys, n, table, d_key_status, pk_xy, d_status, d_count, d_agg48, st);
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     if (group == 0)
         launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + f.ls), reinterpret_cast<Fp*>(base + f.lh), d_status, d_result, st);
     else
@@ -1498,6 +1522,11 @@ int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const u
                              reinterpret_cast<Fp*>(base + f.g.sum), reinterpret_cast<int32_t*>(base + f.g.gflag), reinterpret_cast<Fp*>(base + f.g.lines_h),
                              reinterpret_cast<Fp*>(base + f.g.lines_g), reinterpret_cast<Fp*>(base + f.g.partials), d_result, st);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_committee_verify_batch(const uint8_t* d_pks48, uint32_t n_keys, const uint8_t* d_bitmap, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n,
+                                const uint64_t* d_scalars, uint32_t group, int32_t* d_result, uint32_t* d_count, int32_t* d_status, int32_t* d_key_status, uint8_t* d_agg48,
+                                void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    return blsw_committee_verify_batch_dst(d_pks48, n_keys, d_bitmap, d_sig96, d_msg, msg_len, n, d_scalars, group, d_result, d_count, d_status, d_key_status, d_agg48, d_workspace, workspace_bytes, nullptr, stream_);
 }
 // ---- a resident key registry and index lists (include/blsw.h; registry.hpp). The caller's buffer: [capacity] 128-byte records, then the status
 // array [capacity] int32, each 256-byte aligned. `size` lives on the host: a call passes it to its kernel, which reads no record at or beyond it.
@@ -1576,10 +1605,10 @@ int blsw_registry_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t 
     *bytes = direct_values_bytes(n, msg_len, registry_verify_offsets(n, group, &f));
     return BLSW_OK;
 }
-int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96, const uint8_t* d_msg,
-                               uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status, uint8_t* d_agg48, void* d_workspace,
-                               uint64_t workspace_bytes, void* stream_) {
-    if (!registry_shape_ok(n, msg_len, group) || !d_sig96 || (!d_msg && msg_len) || !d_result || !d_status || !d_workspace ||
+int blsw_registry_verify_batch_dst(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96, const uint8_t* d_msg,
+                                   uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status, uint8_t* d_agg48, void* d_workspace,
+                                   uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !registry_shape_ok(n, msg_len, group) || !d_sig96 || (!d_msg && msg_len) || !d_result || !d_status || !d_workspace ||
         (group == 0 ? d_scalars != nullptr : d_scalars == nullptr) || !r || !d_offsets || (!d_indices && n_indices) || n_indices > (1ull << 40) || r->size == 0)
         return BLSW_ERR_ARG;
     CommitteeOffsets f;
@@ -1593,7 +1622,7 @@ int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indic
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, off_ws, st, &g)) return rc;
     launch_committee_decode(nullptr, 0, d_sig96, n, nullptr, nullptr, sig_xy, d_status, st);  // no keys: its n signature lanes alone, status[i][1]
     launch_registry_sum(r->records, r->size, d_indices, n_indices, d_offsets, n, pk_xy, d_status, d_agg48, st);
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     if (group == 0)
         launch_verify_values(n, g.ws, pk_xy, sig_xy, reinterpret_cast<Fp*>(base + f.ls), reinterpret_cast<Fp*>(base + f.lh), d_status, d_result, st);
     else
@@ -1602,17 +1631,79 @@ int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indic
                              reinterpret_cast<Fp*>(base + f.g.lines_g), reinterpret_cast<Fp*>(base + f.g.partials), d_result, st);
     return hip_ok(hipGetLastError(), "launch");
 }
+int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96, const uint8_t* d_msg,
+                               uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status, uint8_t* d_agg48, void* d_workspace,
+                               uint64_t workspace_bytes, void* stream_) {
+    return blsw_registry_verify_batch_dst(r, d_indices, n_indices, d_offsets, d_sig96, d_msg, msg_len, n, d_scalars, group, d_result, d_status, d_agg48, d_workspace, workspace_bytes, nullptr, stream_);
+}
 // BLS::sign + PublicKey::from(&sk) for a batch (bls.rs:411-425, 183-195). Workspace: blsw_hash_to_g2_workspace_bytes.
-int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
-                    uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
-    if (!d_sk32_le || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_status || msg_len > 65535) return BLSW_ERR_ARG;
+int blsw_sign_batch_dst(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
+                        uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {
+    if (!dst_ok(dst) || !d_sk32_le || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_workspace || !d_status || msg_len > 65535) return BLSW_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
     DeviceGuard guard(stream_device(st));  // the device that owns `stream`
     Group g;
     if (int rc = direct_values_group(d_msg, msg_len, n, d_workspace, workspace_bytes, 256, st, &g)) return rc;
-    launch_values_hash(g, st);
+    launch_values_hash(g, st, dst);
     hipLaunchKernelGGL(k_sign, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, n, g.ws, d_sk32_le, d_sig96, d_sig_xy, d_pk48, d_pk_xy, d_status);
     return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_sign_batch(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
+                    uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    return blsw_sign_batch_dst(d_sk32_le, d_msg, msg_len, n, d_sig96, d_sig_xy, d_pk48, d_pk_xy, d_status, d_workspace, workspace_bytes, nullptr, stream_);
+}
+// ---- domain separation tags (include/blsw.h) and the two proof-of-possession algorithms of the signature draft's POP ciphersuite
+int blsw_dst_set(blsw_dst_t* out, const uint8_t* tag, uint32_t len) {
+    if (!out || !tag || len == 0 || len > BLSW_DST_MAX) return BLSW_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    memcpy(out->bytes, tag, len);
+    out->len = (uint8_t)len;
+    return BLSW_OK;
+}
+int blsw_dst_default(blsw_dst_t* out) { return blsw_dst_set(out, reinterpret_cast<const uint8_t*>(BLSW_DST), BLSW_DST_LEN); }
+int blsw_dst_pop(blsw_dst_t* out) {
+    static const char pop[] = "BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_";
+    return blsw_dst_set(out, reinterpret_cast<const uint8_t*>(pop), sizeof(pop) - 1);
+}
+// hash_to_field alone: no workspace, the messages and the outputs are the caller's arrays (k_sha_values_dst's second form)
+int blsw_hash_to_field_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const blsw_dst_t* dst, uint64_t* d_u, void* stream_) {
+    if (!dst_ok(dst) || (!d_msg && msg_len) || n == 0 || n > 0x7fffffffu || !d_u || msg_len > 65535) return BLSW_ERR_ARG;
+    blsw_dst_t lib_tag;
+    if (!dst) {
+        blsw_dst_default(&lib_tag);
+        dst = &lib_tag;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    Group g = {};  // N and msg_len are all this form of the kernel reads
+    g.N = n;
+    g.msg_len = msg_len;
+    DstArg a;
+    dst_arg_build(&a, dst->bytes, dst->len, msg_len);
+    hipLaunchKernelGGL(k_sha_values_dst, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, g, a, d_msg, reinterpret_cast<Fp*>(d_u));
+    return hip_ok(hipGetLastError(), "launch");
+}
+// PopProve: the keys first (their bytes are the messages), the hash under the POP tag, then k_sign's signature lanes. Workspace: blsw_hash_to_g2_workspace_bytes(n, 48).
+int blsw_pop_prove_batch(const uint8_t* d_sk32_le, uint64_t n, uint8_t* d_proof96, uint8_t* d_pk48, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes,
+                         void* stream_) {
+    if (!d_sk32_le || n == 0 || n > 0x7fffffffu || !d_proof96 || !d_pk48 || !d_status || !d_workspace) return BLSW_ERR_ARG;
+    blsw_dst_t pop;
+    blsw_dst_pop(&pop);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    Group g;
+    if (int rc = direct_values_group(d_pk48, 48, n, d_workspace, workspace_bytes, 256, st, &g)) return rc;
+    hipLaunchKernelGGL(k_pop_pk, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, d_sk32_le, d_pk48);
+    launch_values_hash(g, st, &pop);
+    hipLaunchKernelGGL(k_sign, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, n, g.ws, d_sk32_le, d_proof96, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint64_t*)nullptr, d_status);
+    return hip_ok(hipGetLastError(), "launch");
+}
+// PopVerify = Verify under the POP tag with the key's own 48 bytes as the message
+int blsw_pop_verify_batch(const uint8_t* d_pk48, const uint8_t* d_proof96, uint64_t n, int32_t* d_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes,
+                          void* stream_) {
+    blsw_dst_t pop;
+    blsw_dst_pop(&pop);
+    return blsw_verify_batch_dst(d_pk48, d_proof96, d_pk48, 48, n, d_result, d_status, d_workspace, workspace_bytes, &pop, stream_);
 }
 int blsw_layout_aggregate(uint32_t msg_len, uint32_t n_keys, blsw_layout_t* out) {
     if (!out || msg_len > 65535) return BLSW_ERR_ARG;

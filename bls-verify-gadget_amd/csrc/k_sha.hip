@@ -43,6 +43,40 @@ __global__ __launch_bounds__(64) void k_sha_values(Group g) {
     for (int j = 0; j < 4; j++) st_fp(g.ws.u + (uint64_t)j * g.N + I, hash_to_field_elem(uw + 16 * j));
 }
 
+// the same under a caller-chosen domain separation tag (sha.hpp: expand_message_values_dst). The tag's words arrive by value, laid out by the
+// host once per call; the block copies them to LDS, where every lane reads them at wave-uniform addresses.
+//   d_u == nullptr: messages and outputs as k_sha_values (the group's step descriptor, g.ws.u rows)
+//   d_u != nullptr: blsw_hash_to_field_batch — messages d_msg [N][msg_len], outputs d_u [N][4] field elements; the group carries N and msg_len only
+__global__ __launch_bounds__(64) void k_sha_values_dst(Group g, DstArg a, const uint8_t* d_msg, Fp* d_u) {
+    __shared__ DstArg sa;
+    static_assert(sizeof(DstArg) % 4 == 0, "copied word by word");
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&a);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&sa);
+        for (uint32_t k = threadIdx.x; k < sizeof(DstArg) / 4; k += 64) dst[k] = src[k];
+    }
+    __syncthreads();
+    if (g.chain_prio) __builtin_amdgcn_s_setprio(3);
+    uint64_t I = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= g.N) return;
+    const uint8_t* msg;
+    if (d_u) {
+        msg = d_msg + I * g.msg_len;
+    } else {
+        LaneId id = lane_id(g, I);
+        msg = g.desc[id.s].msg + (uint64_t)id.f * g.msg_len;
+    }
+    uint32_t uw[64];
+    expand_message_values_dst(msg, &sa, uw);
+    for (int j = 0; j < 4; j++) {
+        const Fp u = hash_to_field_elem(uw + 16 * j);
+        if (d_u)
+            st_fp(d_u + 4 * I + j, u);
+        else
+            st_fp(g.ws.u + (uint64_t)j * g.N + I, u);
+    }
+}
+
 #endif
 
 }  // namespace blsw

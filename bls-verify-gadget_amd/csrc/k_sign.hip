@@ -61,4 +61,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
+// PopProve's first half (blsw_pop_prove_batch): pk_i = sk_i * g1 as compressed bytes, k_sign's key lanes alone — the proof's message is these
+// bytes, so they exist before the hash runs. A key that is not a valid secret key gives the infinity encoding, as there.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_pop_pk(uint64_t n, const uint8_t* __restrict__ sk32, uint8_t* pk48) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t k[8];
+    const int st = sk_from_le32(sk32 + i * 32, k);
+    Fp x = fp_zero(), y = fp_zero();
+    bool inf = true;
+    if (st == SIGN_OK) {
+        const Jac1v acc = v1_mul_g1_fixed(k);
+        if (!fp_is_zero(acc.z)) {
+            const Fp ai = fp_inv(acc.z), ai2 = fp_sqr(ai);
+            x = fp_mul(acc.x, ai2);
+            y = fp_mul(acc.y, fp_mul(ai2, ai));
+            inf = false;
+        }
+    }
+    g1_encode(x, y, inf, pk48 + i * 48);
+}
+
 }  // namespace blsw

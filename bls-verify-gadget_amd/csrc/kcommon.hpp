@@ -627,6 +627,7 @@ __global__ void k_cofv_dbl_w(Group g);
 __global__ void k_cofv_add_w(Group g);
 __global__ void k_cofv_join(Group g);
 __global__ void k_sha_values(Group g);
+__global__ void k_sha_values_dst(Group g, DstArg a, const uint8_t* d_msg, Fp* d_u);
 __global__ void k_msg_input(Group g);
 __global__ void k_agg_instance(Group g, uint32_t n_elems, uint32_t s0);
 __global__ void k_map_values(Group g);
@@ -646,6 +647,7 @@ __global__ void k_h_to_affine(uint64_t n, Workspace ws, uint64_t* d_out);
 __global__ void k_decode_points(uint32_t group, const uint8_t* __restrict__ in, uint64_t m, Fp* xy, int32_t* st);
 __global__ void k_sum_points(uint32_t group, const Fp* __restrict__ xy, const int32_t* __restrict__ pst, uint32_t k, uint64_t n, uint8_t* out, int32_t* status);
 __global__ void k_sign(uint64_t n, Workspace ws, const uint8_t* __restrict__ sk32, uint8_t* sig96, uint64_t* sig_xy, uint8_t* pk48, uint64_t* pk_xy, int32_t* status);
+__global__ void k_pop_pk(uint64_t n, const uint8_t* __restrict__ sk32, uint8_t* pk48);
 __global__ void k_bench_mad(uint32_t iters, uint32_t* out);
 __global__ void k_bench_fill(uint4* __restrict__ dst, uint64_t n16);
 __global__ void k_bench_fpmul(uint32_t iters, uint32_t* out);

@@ -640,4 +640,108 @@ BLSW_FN Fp hash_to_field_elem(const uint32_t* W /*16 big-endian words*/) {
     return fp_add(fp_mul(hm, km), tm);
 }
 
+// ---- value-only expand_message_xmd under a CALLER-CHOSEN domain separation tag of 1 .. 255 bytes (the *_dst entries of include/blsw.h).
+// The tag and msg_len are the same for every lane of a call, so every tag byte sits at a wave-uniform position of every block: the host lays
+// the constant words out ONCE per call (DstArg, a kernel argument) and the lanes do word operations only — no per-lane byte array.
+//   b_0 = H(Z_pad(64) | msg | I2OSP(256, 2) | 0 | DST | L | padding):  ceil((77 + msg_len + L) / 64) blocks, the first of them all zero
+//   b_i = H((b_0 ^ b_(i-1))(32) | i | DST | L | padding):              ceil((43 + L) / 64) = 1 .. 5 blocks
+#define BLSW_DST_MAX 255
+#define BLSW_DST_B0_SUFFIX_WORDS 84  // (msg_len % 4) + 3 + L + 1 + 9 bytes and at most 63 of padding: < 335 bytes, whole words
+#define BLSW_DST_BI_TAIL_WORDS 72    // 5 blocks less the 8 words of the chained digest
+struct DstArg {
+    uint32_t zpad[8];     // the SHA-256 state after the all-zero Z_pad block
+    uint32_t b0_blocks;   // blocks of b_0 behind Z_pad
+    uint32_t msg_words;   // msg_len / 4: the whole big-endian words of a message
+    uint32_t msg_rem;     // msg_len % 4: message bytes in the word the suffix starts in
+    uint32_t bi_blocks;   // blocks of every b_i
+    uint32_t b0_suffix[BLSW_DST_B0_SUFFIX_WORDS];  // I2OSP(256, 2) | 0 | DST | L | 0x80 | 0 .. | bit length, big-endian words, shifted by msg_rem bytes (zeros in front)
+    uint32_t bi_tail[BLSW_DST_BI_TAIL_WORDS];      // words 8 .. of b_i's blocks: i (as 0: the lanes OR it in) | DST | L | 0x80 | 0 .. | bit length
+};
+// host: the argument of one call. 0, or -1 for a tag length outside 1 .. 255 (RFC 9380 5.3.3's hashing of longer tags is not offered).
+inline int dst_arg_build(DstArg* a, const uint8_t* dst, uint32_t dst_len, uint32_t msg_len) {
+    constexpr uint32_t H0[8] = BLSW_SHA_H0;
+    if (!a || !dst || dst_len == 0 || dst_len > BLSW_DST_MAX) return -1;
+    *a = DstArg();
+    uint32_t zero[16] = {};
+    for (int i = 0; i < 8; i++) a->zpad[i] = H0[i];
+    sha256_compress_plain(a->zpad, zero);
+    const uint32_t r = msg_len % 4, mw = msg_len / 4;
+    const uint64_t total = 64ull + msg_len + 3 + dst_len + 1, padded = (total + 9 + 63) / 64 * 64;
+    a->b0_blocks = (uint32_t)(padded / 64 - 1);
+    a->msg_words = mw;
+    a->msg_rem = r;
+    uint8_t sb[4 * BLSW_DST_B0_SUFFIX_WORDS] = {};
+    const uint32_t nb = (uint32_t)(padded - 64 - 4ull * mw);  // <= r + dst_len + 76, a multiple of 4
+    uint32_t p = r;
+    sb[p++] = 0x01;  // I2OSP(256, 2)
+    sb[p++] = 0x00;
+    sb[p++] = 0x00;
+    for (uint32_t k = 0; k < dst_len; k++) sb[p++] = dst[k];
+    sb[p++] = (uint8_t)dst_len;
+    sb[p++] = 0x80;
+    for (int k = 0; k < 8; k++) sb[nb - 1 - k] = (uint8_t)((total * 8) >> (8 * k));
+    for (uint32_t k = 0; k < nb / 4; k++) a->b0_suffix[k] = ((uint32_t)sb[4 * k] << 24) | ((uint32_t)sb[4 * k + 1] << 16) | ((uint32_t)sb[4 * k + 2] << 8) | sb[4 * k + 3];
+    const uint32_t itotal = 32 + 1 + dst_len + 1, ipadded = (itotal + 9 + 63) / 64 * 64;
+    a->bi_blocks = ipadded / 64;
+    uint8_t tb[4 * BLSW_DST_BI_TAIL_WORDS] = {};
+    const uint32_t tn = ipadded - 32;
+    p = 1;  // byte 0: i
+    for (uint32_t k = 0; k < dst_len; k++) tb[p++] = dst[k];
+    tb[p++] = (uint8_t)dst_len;
+    tb[p++] = 0x80;
+    tb[tn - 2] = (uint8_t)((itotal * 8) >> 8);
+    tb[tn - 1] = (uint8_t)(itotal * 8);
+    for (uint32_t k = 0; k < tn / 4; k++) a->bi_tail[k] = ((uint32_t)tb[4 * k] << 24) | ((uint32_t)tb[4 * k + 1] << 16) | ((uint32_t)tb[4 * k + 2] << 8) | tb[4 * k + 3];
+    return 0;
+}
+// `a` is wave-uniform (on the device: the block's copy of the kernel argument in LDS); the message length is a's
+BLSW_FN void expand_message_values_dst(const uint8_t* msg, const DstArg* a, uint32_t uniform_words[64]) {
+    constexpr uint32_t H0[8] = BLSW_SHA_H0;
+    const uint32_t mw = a->msg_words, r = a->msg_rem, nb0 = a->b0_blocks, nbi = a->bi_blocks;
+    uint32_t st[8];
+    for (int i = 0; i < 8; i++) st[i] = a->zpad[i];
+#pragma unroll 1
+    for (uint32_t blk = 0; blk < nb0; blk++) {
+        uint32_t data[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const uint32_t w = blk * 16 + j;
+            uint32_t v;
+            if (w < mw) {
+                const uint8_t* m = msg + 4ull * w;
+                v = ((uint32_t)m[0] << 24) | ((uint32_t)m[1] << 16) | ((uint32_t)m[2] << 8) | m[3];
+            } else {
+                v = a->b0_suffix[w - mw];  // w - mw < the suffix's words: b0_blocks * 16 - mw of them
+                if (w == mw)
+                    for (uint32_t b = 0; b < r; b++) v |= (uint32_t)msg[4ull * mw + b] << (24 - 8 * b);
+            }
+            data[j] = v;
+        }
+        sha256_compress_plain(st, data);
+    }
+    uint32_t b0[8], last[8];
+    for (int i = 0; i < 8; i++) b0[i] = last[i] = st[i];
+#pragma unroll 1
+    for (uint32_t i = 1; i <= 8; i++) {
+        uint32_t data[16];
+#pragma unroll
+        for (int k = 0; k < 8; k++) data[k] = (i == 1) ? b0[k] : (b0[k] ^ last[k]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) data[8 + k] = a->bi_tail[k];
+        data[8] |= i << 24;
+        for (int k = 0; k < 8; k++) st[k] = H0[k];
+        sha256_compress_plain(st, data);
+#pragma unroll 1
+        for (uint32_t blk = 1; blk < nbi; blk++) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) data[k] = a->bi_tail[16 * blk - 8 + k];
+            sha256_compress_plain(st, data);
+        }
+        for (int k = 0; k < 8; k++) {
+            last[k] = st[k];
+            uniform_words[(i - 1) * 8 + k] = st[k];
+        }
+    }
+}
+
 }  // namespace blsw

@@ -820,6 +820,68 @@ int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indic
                                const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status,
                                uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
+/* A CALLER-CHOSEN DOMAIN SEPARATION TAG for the value entries, and PopProve / PopVerify. New symbols only: the ABI number stays 17 and
+ * blsw_engine_options_t is untouched. Every entry above hashes under the library's tag, BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_; the *_dst
+ * entries below take the tag of hash_to_curve (RFC 9380 5.3.1, expand_message_xmd with SHA-256) as an argument, so that the proof-of-possession tag
+ * BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_ of the signature draft, the ..._NUL_ and ..._AUG_ suites' tags and application tags can be used.
+ *   blsw_dst_t: the tag's bytes and its length, 1 .. 255. A tag of more than 255 bytes (RFC 9380 5.3.3 hashes it down first) is NOT offered.
+ *   blsw_dst_set: BLSW_ERR_ARG for a NULL argument, len == 0 or len > 255 (BLSW_DST_MAX_LEN); bytes behind the tag are zeroed.
+ *   blsw_dst_default / blsw_dst_pop: the library's tag / the BLS_POP_... tag (43 bytes each).
+ * The tag travels to the device as a KERNEL ARGUMENT laid out on the host once per call (csrc/sha.hpp: DstArg), so every *_dst entry takes the
+ * workspace of its plain form. `dst` == NULL is the plain entry exactly (the same kernels, the same bits); a non-NULL tag always runs the
+ * tag-taking hash kernel, also when it equals the library's tag — the results are the same bits. A non-NULL tag of length 0 is BLSW_ERR_ARG.
+ * Everything else — arguments, statuses, verdicts, properties, errors — is word for word the plain entry's. b_0 of a message hashes
+ * ceil((77 + msg_len + len) / 64) blocks and each of the eight b_i ceil((43 + len) / 64): 1 block up to 21 tag bytes, 2 up to 85 (the library's
+ * tag), 3 up to 149, 4 up to 213, 5 up to 255.
+ * What stays out: the tag of the witness engine and the circuits (constant bits folded into the SHA gadget: another tag is another circuit);
+ * tags beyond 255 bytes; messages of different lengths in one call; a registry that admits keys only with a proof of possession
+ * (blsw_registry_append is unchanged: callers run blsw_pop_verify_batch first). */
+#define BLSW_DST_MAX_LEN 255
+typedef struct {
+    uint8_t bytes[255];
+    uint8_t len;
+} blsw_dst_t;
+int blsw_dst_set(blsw_dst_t* out, const uint8_t* tag, uint32_t len);
+int blsw_dst_default(blsw_dst_t* out);
+int blsw_dst_pop(blsw_dst_t* out);
+/* hash_to_field of RFC 9380 5.2 for G2 (count 2, m 2, L 64) on its own: d_msg [n][msg_len] -> d_u [n][4][6] u64 Montgomery in the order u0.c0, u0.c1,
+ * u1.c0, u1.c1 — the only thing the tag changes in any entry. No workspace, no descriptor copy: asynchronous on `stream`. dst == NULL = the
+ * library's tag. BLSW_ERR_ARG: n == 0 or > 0x7fffffff, msg_len > 65535, d_u == NULL, d_msg == NULL with msg_len != 0, a tag of length 0. */
+int blsw_hash_to_field_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const blsw_dst_t* dst, uint64_t* d_u, void* stream);
+int blsw_hash_to_g2_batch_dst(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
+                              const blsw_dst_t* dst, void* stream);
+int blsw_sign_batch_dst(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
+                        uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream);
+int blsw_verify_batch_dst(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, int32_t* d_result,
+                          int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream);
+int blsw_verify_groups_batch_dst(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars,
+                                 uint32_t group, int32_t* d_group_result, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes,
+                                 const blsw_dst_t* dst, void* stream);
+int blsw_verify_pairs_batch_dst(const uint8_t* d_pks48, const uint8_t* d_msgs, uint32_t msg_len, uint32_t n_pairs, const uint32_t* d_counts,
+                                const uint8_t* d_sig96, uint64_t n, int32_t* d_result, int32_t* d_status, int32_t* d_key_status, void* d_workspace,
+                                uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream);
+int blsw_committee_verify_batch_dst(const uint8_t* d_pks48, uint32_t n_keys, const uint8_t* d_bitmap, const uint8_t* d_sig96, const uint8_t* d_msg,
+                                    uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, uint32_t* d_count,
+                                    int32_t* d_status, int32_t* d_key_status, uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes,
+                                    const blsw_dst_t* dst, void* stream);
+int blsw_registry_verify_batch_dst(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96,
+                                   const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result,
+                                   int32_t* d_status, uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream);
+/* PopProve of the signature draft (POP ciphersuite) for a batch: pk_i = sk_i * g1 and proof_i = sk_i * H_pop(pk_i's 48 compressed bytes), H_pop =
+ * hash_to_g2 under the BLS_POP_... tag.
+ *   d_sk32_le [n][32] as blsw_sign_batch takes them; d_proof96 [n][96], d_pk48 [n][48] compressed, both REQUIRED (the key bytes are the proof's
+ *   message); d_status [n] int32 exactly blsw_sign_batch's: BLSW_ST_OK, BLSW_ST_BAD_ENCODING (sk >= r) or BLSW_ST_INVALID_SECRET_KEY (sk = 0),
+ *   and on error both outputs of the instance are the infinity encoding.
+ * Workspace: blsw_hash_to_g2_workspace_bytes(n, 48). BLSW_ERR_ARG: n == 0 or > 0x7fffffff, a NULL pointer. */
+int blsw_pop_prove_batch(const uint8_t* d_sk32_le, uint64_t n, uint8_t* d_proof96, uint8_t* d_pk48, int32_t* d_status, void* d_workspace,
+                         uint64_t workspace_bytes, void* stream);
+/* PopVerify for a batch: KeyValidate (the key decodes, lies in the prime-order subgroup and is not the identity), the proof decodes the same way, and
+ * e(-g1, proof) * e(pk, H_pop(pk48)) == 1. It IS blsw_verify_batch_dst with the key bytes as the message and the BLS_POP_... tag: d_result [n],
+ * d_status [n][2] (key, proof), arguments and errors as there. Workspace: blsw_verify_workspace_bytes(n, 48). A signature over the key bytes made
+ * under the library's tag is refused: that is what the second tag is for. */
+int blsw_pop_verify_batch(const uint8_t* d_pk48, const uint8_t* d_proof96, uint64_t n, int32_t* d_result, int32_t* d_status, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
+
 /* Device micro-benchmarks that give the VALU roofline its MEASURED denominator:
  * which = 0: v_mad_u64_u32 rate (32x32+64 multiply-adds per second, all CUs); 1: Fp Montgomery products per second;
  * 2: Fp inversions (safegcd) per second; 3: Fp products per second inside witness-emitting Fp2 mul + sqr;

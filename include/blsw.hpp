@@ -850,7 +850,35 @@ struct BlsSignatureVerifyGadget {
     }
 };
 
+// The domain separation tag of hash_to_curve for the BLS:: value functions (blsw_dst_t, include/blsw.h): 1 .. 255 bytes. A default-constructed Dst
+// is "the library's tag through the plain entry" (get() == nullptr); Dst::pop() is the proof-of-possession tag of the signature draft.
+class Dst {
+public:
+    Dst() = default;
+    explicit Dst(const std::string& tag) : set_(true) { check(blsw_dst_set(&t_, reinterpret_cast<const uint8_t*>(tag.data()), (uint32_t)tag.size()), "blsw_dst_set"); }
+    explicit Dst(const std::vector<uint8_t>& tag) : set_(true) { check(blsw_dst_set(&t_, tag.data(), (uint32_t)tag.size()), "blsw_dst_set"); }
+    static Dst library() {
+        Dst d;
+        d.set_ = true;
+        check(blsw_dst_default(&d.t_), "blsw_dst_default");
+        return d;
+    }
+    static Dst pop() {
+        Dst d;
+        d.set_ = true;
+        check(blsw_dst_pop(&d.t_), "blsw_dst_pop");
+        return d;
+    }
+    const blsw_dst_t* get() const { return set_ ? &t_ : nullptr; }
+    std::vector<uint8_t> bytes() const { return set_ ? std::vector<uint8_t>(t_.bytes, t_.bytes + t_.len) : Dst::library().bytes(); }
+
+private:
+    blsw_dst_t t_{};
+    bool set_ = false;
+};
+
 // The native scheme (src/bls.rs:395-458, `impl SignatureScheme for BLS`) for batches: one secret key / message / signature per element.
+// Every function takes the tag as its last argument: the default is the library's (the plain C entry, exactly as before).
 struct SecretKey {
     std::array<uint8_t, 32> le;  // PrivateKey::try_from(&[u8]) (bls.rs:97-103): little-endian Fr
     static SecretKey try_from(const std::string& hex_be) {  // the fixtures' big-endian hex ("0x..." allowed)
@@ -867,7 +895,7 @@ struct BLS {
         std::vector<int32_t> status;          // BLSW_ST_OK, BLSW_ST_INVALID_SECRET_KEY (sk = 0: Err(InvalidSecretKey), bls.rs:417-419), BLSW_ST_BAD_ENCODING (sk >= r)
     };
     // BLS::sign (bls.rs:411-425) and PublicKey::from(&sk) (bls.rs:183-195): messages [n][msg_len]
-    static Signed sign(const Parameters&, const std::vector<SecretKey>& sks, const std::vector<std::vector<uint8_t>>& messages) {
+    static Signed sign(const Parameters&, const std::vector<SecretKey>& sks, const std::vector<std::vector<uint8_t>>& messages, const Dst& dst = Dst()) {
         const size_t n = sks.size();
         if (n == 0 || messages.size() != n) throw Error("BLS::sign: one message per key", BLSW_ERR_ARG);
         const uint32_t msg_len = (uint32_t)messages[0].size();
@@ -882,8 +910,8 @@ struct BLS {
         detail::DeviceBytes d_sk(sk.size()), d_msg(msg.size()), d_sig(n * 96), d_pk(n * 48), d_st(n * 4), ws(bytes);
         d_sk.upload(sk.data(), sk.size());
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
-        check(blsw_sign_batch(static_cast<const uint8_t*>(d_sk.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n, static_cast<uint8_t*>(d_sig.get()), nullptr,
-                              static_cast<uint8_t*>(d_pk.get()), nullptr, static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+        check(blsw_sign_batch_dst(static_cast<const uint8_t*>(d_sk.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n, static_cast<uint8_t*>(d_sig.get()), nullptr,
+                              static_cast<uint8_t*>(d_pk.get()), nullptr, static_cast<int32_t*>(d_st.get()), ws.get(), bytes, dst.get(), nullptr),
               "blsw_sign_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<uint8_t> sg(n * 96), pk(n * 48);
@@ -903,7 +931,7 @@ struct BLS {
     // BLS::verify (bls.rs:427-458) for n (pk, msg, sig) triples: the native pairing check as values (no circuit, no witness tensor).
     // An identity or undecodable key / signature is Err(..) in the reference and `false` here, with the reason in `status` ([n][2], BLSW_ST_*).
     static std::vector<bool> verify(const Parameters&, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
-                                    const std::vector<Signature>& sigs, std::vector<int32_t>* status = nullptr) {
+                                    const std::vector<Signature>& sigs, std::vector<int32_t>* status = nullptr, const Dst& dst = Dst()) {
         const size_t n = pks.size();
         if (n == 0 || messages.size() != n || sigs.size() != n) throw Error("BLS::verify: one message and one signature per key", BLSW_ERR_ARG);
         const uint32_t msg_len = (uint32_t)messages[0].size();
@@ -921,8 +949,8 @@ struct BLS {
         d_sg.upload(sg.data(), sg.size());
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
         // the native algorithm as values (blsw_verify_batch): decode + subgroup checks, hash to G2, projective two-pair Miller loop, final exponentiation
-        check(blsw_verify_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
-                                static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+        check(blsw_verify_batch_dst(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
+                                static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes, dst.get(), nullptr),
               "blsw_verify_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n);
@@ -950,7 +978,7 @@ struct BLS {
     // scalars: empty draws group_scalars(n); given ones are used as they are, and predictable ones are NOT sound (include/blsw.h, P4).
     static std::vector<bool> verify_groups(const Parameters&, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
                                            const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
-                                           std::vector<int32_t>* status = nullptr) {
+                                           std::vector<int32_t>* status = nullptr, const Dst& dst = Dst()) {
         const size_t n = pks.size();
         if (n == 0 || messages.size() != n || sigs.size() != n || group == 0) throw Error("BLS::verify_groups: one message and one signature per key", BLSW_ERR_ARG);
         if (scalars.empty()) scalars = group_scalars(n);
@@ -971,9 +999,9 @@ struct BLS {
         d_sg.upload(sg.data(), sg.size());
         d_sc.upload(scalars.data(), n * 8);
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
-        check(blsw_verify_groups_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
+        check(blsw_verify_groups_batch_dst(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
                                        static_cast<const uint64_t*>(d_sc.get()), group, static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes,
-                                       nullptr),
+                                       dst.get(), nullptr),
               "blsw_verify_groups_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n_groups);
@@ -990,8 +1018,8 @@ struct BLS {
     // most groups hold a bad triple is slower this way than verify.
     static std::vector<bool> verify_grouped(const Parameters& params, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
                                             const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
-                                            std::vector<int32_t>* status = nullptr) {
-        const std::vector<bool> g = verify_groups(params, pks, messages, sigs, group, std::move(scalars), status);
+                                            std::vector<int32_t>* status = nullptr, const Dst& dst = Dst()) {
+        const std::vector<bool> g = verify_groups(params, pks, messages, sigs, group, std::move(scalars), status, dst);
         const size_t n = pks.size();
         std::vector<bool> out(n, true);
         std::vector<size_t> idx;
@@ -1006,7 +1034,7 @@ struct BLS {
             m2.push_back(messages[i]);
             s2.push_back(sigs[i]);
         }
-        const std::vector<bool> r = verify(params, p2, m2, s2);
+        const std::vector<bool> r = verify(params, p2, m2, s2, nullptr, dst);
         for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
         return out;
     }
@@ -1019,7 +1047,7 @@ struct BLS {
                                                              const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& sigs, uint32_t group = 0,
                                                              std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr,
                                                              std::vector<int32_t>* key_status = nullptr, std::vector<uint32_t>* counts = nullptr,
-                                                             std::vector<PublicKey>* aggregates = nullptr) {
+                                                             std::vector<PublicKey>* aggregates = nullptr, const Dst& dst = Dst()) {
         const size_t n = bitmaps.size(), K = committee.size();
         if (n == 0 || K == 0 || K > 65535 || messages.size() != n || sigs.size() != n)
             throw Error("BLS::fast_aggregate_verify_committee: a committee, and one bitmap, message and signature per instance", BLSW_ERR_ARG);
@@ -1047,10 +1075,10 @@ struct BLS {
         d_sg.upload(sg.data(), sg.size());
         if (group) d_sc.upload(scalars.data(), n * 8);
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
-        check(blsw_committee_verify_batch(static_cast<const uint8_t*>(d_pk.get()), (uint32_t)K, static_cast<const uint8_t*>(d_bm.get()), static_cast<const uint8_t*>(d_sg.get()),
+        check(blsw_committee_verify_batch_dst(static_cast<const uint8_t*>(d_pk.get()), (uint32_t)K, static_cast<const uint8_t*>(d_bm.get()), static_cast<const uint8_t*>(d_sg.get()),
                                           static_cast<const uint8_t*>(d_msg.get()), msg_len, n, group ? static_cast<const uint64_t*>(d_sc.get()) : nullptr, group,
                                           static_cast<int32_t*>(d_res.get()), static_cast<uint32_t*>(d_cnt.get()), static_cast<int32_t*>(d_st.get()),
-                                          static_cast<int32_t*>(d_kst.get()), static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, nullptr),
+                                          static_cast<int32_t*>(d_kst.get()), static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, dst.get(), nullptr),
               "blsw_committee_verify_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n_res);
@@ -1082,9 +1110,9 @@ struct BLS {
     static std::vector<bool> fast_aggregate_verify_committee_grouped(const Parameters& params, const std::vector<PublicKey>& committee,
                                                                      const std::vector<std::vector<uint8_t>>& bitmaps, const std::vector<std::vector<uint8_t>>& messages,
                                                                      const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
-                                                                     std::vector<int32_t>* status = nullptr) {
+                                                                     std::vector<int32_t>* status = nullptr, const Dst& dst = Dst()) {
         if (group == 0) throw Error("BLS::fast_aggregate_verify_committee_grouped: group >= 1", BLSW_ERR_ARG);
-        const std::vector<bool> g = fast_aggregate_verify_committee(params, committee, bitmaps, messages, sigs, group, std::move(scalars), status);
+        const std::vector<bool> g = fast_aggregate_verify_committee(params, committee, bitmaps, messages, sigs, group, std::move(scalars), status, nullptr, nullptr, nullptr, dst);
         const size_t n = bitmaps.size();
         std::vector<bool> out(n, true);
         std::vector<size_t> idx;
@@ -1098,7 +1126,7 @@ struct BLS {
             m2.push_back(messages[i]);
             s2.push_back(sigs[i]);
         }
-        const std::vector<bool> r = fast_aggregate_verify_committee(params, committee, b2, m2, s2);
+        const std::vector<bool> r = fast_aggregate_verify_committee(params, committee, b2, m2, s2, 0, {}, nullptr, nullptr, nullptr, nullptr, dst);
         for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
         return out;
     }
@@ -1110,7 +1138,7 @@ struct BLS {
     static std::vector<bool> fast_aggregate_verify_indexed(const Parameters&, const KeyRegistry& registry, const std::vector<std::vector<uint32_t>>& index_lists,
                                                            const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& sigs, uint32_t group = 0,
                                                            std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr,
-                                                           std::vector<PublicKey>* aggregates = nullptr) {
+                                                           std::vector<PublicKey>* aggregates = nullptr, const Dst& dst = Dst()) {
         const size_t n = index_lists.size();
         if (n == 0 || messages.size() != n || sigs.size() != n)
             throw Error("BLS::fast_aggregate_verify_indexed: one index list, message and signature per set", BLSW_ERR_ARG);
@@ -1138,10 +1166,10 @@ struct BLS {
         d_sg.upload(sg.data(), sg.size());
         if (group) d_sc.upload(scalars.data(), n * 8);
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
-        check(blsw_registry_verify_batch(registry.get(), idx.empty() ? nullptr : static_cast<const uint32_t*>(d_idx.get()), idx.size(), static_cast<const uint64_t*>(d_off.get()),
+        check(blsw_registry_verify_batch_dst(registry.get(), idx.empty() ? nullptr : static_cast<const uint32_t*>(d_idx.get()), idx.size(), static_cast<const uint64_t*>(d_off.get()),
                                          static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n,
                                          group ? static_cast<const uint64_t*>(d_sc.get()) : nullptr, group, static_cast<int32_t*>(d_res.get()), static_cast<int32_t*>(d_st.get()),
-                                         static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, nullptr),
+                                         static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, dst.get(), nullptr),
               "blsw_registry_verify_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n_res);
@@ -1164,9 +1192,9 @@ struct BLS {
     // registry is not decoded again: it is resident). Slower than group == 0 when most groups hold a bad set.
     static std::vector<bool> fast_aggregate_verify_indexed_grouped(const Parameters& params, const KeyRegistry& registry, const std::vector<std::vector<uint32_t>>& index_lists,
                                                                    const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& sigs, uint32_t group = 64,
-                                                                   std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr) {
+                                                                   std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr, const Dst& dst = Dst()) {
         if (group == 0) throw Error("BLS::fast_aggregate_verify_indexed_grouped: group >= 1", BLSW_ERR_ARG);
-        const std::vector<bool> g = fast_aggregate_verify_indexed(params, registry, index_lists, messages, sigs, group, std::move(scalars), status);
+        const std::vector<bool> g = fast_aggregate_verify_indexed(params, registry, index_lists, messages, sigs, group, std::move(scalars), status, nullptr, dst);
         const size_t n = index_lists.size();
         std::vector<bool> out(n, true);
         std::vector<size_t> idx;
@@ -1181,7 +1209,7 @@ struct BLS {
             m2.push_back(messages[i]);
             s2.push_back(sigs[i]);
         }
-        const std::vector<bool> r = fast_aggregate_verify_indexed(params, registry, l2, m2, s2);
+        const std::vector<bool> r = fast_aggregate_verify_indexed(params, registry, l2, m2, s2, 0, {}, nullptr, nullptr, dst);
         for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
         return out;
     }
@@ -1192,7 +1220,7 @@ struct BLS {
     // status [n][2] (the instance's keys and count, the signature) and key_status [n][longest] (every key, the padding included) are filled when given.
     static std::vector<bool> aggregate_verify(const Parameters&, const std::vector<std::vector<PublicKey>>& key_lists,
                                               const std::vector<std::vector<std::vector<uint8_t>>>& message_lists, const std::vector<Signature>& sigs,
-                                              std::vector<int32_t>* status = nullptr, std::vector<int32_t>* key_status = nullptr) {
+                                              std::vector<int32_t>* status = nullptr, std::vector<int32_t>* key_status = nullptr, const Dst& dst = Dst()) {
         const size_t n = key_lists.size();
         if (n == 0 || message_lists.size() != n || sigs.size() != n) throw Error("BLS::aggregate_verify: one key list, message list and signature per instance", BLSW_ERR_ARG);
         size_t K = 1, msg_len = 0;
@@ -1224,9 +1252,9 @@ struct BLS {
         if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
         d_sg.upload(sg.data(), sg.size());
         d_cnt.upload(counts.data(), n * 4);
-        check(blsw_verify_pairs_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_msg.get()), (uint32_t)msg_len, (uint32_t)K,
+        check(blsw_verify_pairs_batch_dst(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_msg.get()), (uint32_t)msg_len, (uint32_t)K,
                                       static_cast<const uint32_t*>(d_cnt.get()), static_cast<const uint8_t*>(d_sg.get()), n, static_cast<int32_t*>(d_res.get()),
-                                      static_cast<int32_t*>(d_st.get()), static_cast<int32_t*>(d_kst.get()), ws.get(), bytes, nullptr),
+                                      static_cast<int32_t*>(d_st.get()), static_cast<int32_t*>(d_kst.get()), ws.get(), bytes, dst.get(), nullptr),
               "blsw_verify_pairs_batch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         std::vector<int32_t> r(n);
@@ -1238,6 +1266,67 @@ struct BLS {
         if (key_status) {
             key_status->resize(n * K);
             d_kst.download(key_status->data(), n * K * 4);
+        }
+        std::vector<bool> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = r[i] == 1;
+        return out;
+    }
+    // PopProve of the signature draft's POP ciphersuite (blsw_pop_prove_batch): the keys and, per key, proof = sk * hash_to_g2(pk's 48 bytes, Dst::pop()).
+    struct Proved {
+        std::vector<PublicKey> public_keys;
+        std::vector<Signature> proofs;   // the infinity encoding where status != BLSW_ST_OK
+        std::vector<int32_t> status;     // as Signed::status
+    };
+    static Proved pop_prove(const Parameters&, const std::vector<SecretKey>& sks) {
+        const size_t n = sks.size();
+        if (n == 0) throw Error("BLS::pop_prove: at least one key", BLSW_ERR_ARG);
+        std::vector<uint8_t> sk(n * 32);
+        for (size_t i = 0; i < n; i++) std::memcpy(&sk[32 * i], sks[i].le.data(), 32);
+        uint64_t bytes = 0;
+        check(blsw_hash_to_g2_workspace_bytes(n, 48, &bytes), "blsw_hash_to_g2_workspace_bytes");
+        detail::DeviceBytes d_sk(sk.size()), d_proof(n * 96), d_pk(n * 48), d_st(n * 4), ws(bytes);
+        d_sk.upload(sk.data(), sk.size());
+        check(blsw_pop_prove_batch(static_cast<const uint8_t*>(d_sk.get()), n, static_cast<uint8_t*>(d_proof.get()), static_cast<uint8_t*>(d_pk.get()),
+                                   static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+              "blsw_pop_prove_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<uint8_t> pr(n * 96), pk(n * 48);
+        Proved out;
+        out.status.resize(n);
+        d_proof.download(pr.data(), pr.size());
+        d_pk.download(pk.data(), pk.size());
+        d_st.download(out.status.data(), n * 4);
+        out.proofs.resize(n);
+        out.public_keys.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(out.proofs[i].bytes.data(), &pr[96 * i], 96);
+            std::memcpy(out.public_keys[i].bytes.data(), &pk[48 * i], 48);
+        }
+        return out;
+    }
+    // PopVerify (blsw_pop_verify_batch): KeyValidate and the pairing check of the proof over the key's own bytes under Dst::pop(); status [n][2] (key, proof)
+    static std::vector<bool> pop_verify(const Parameters&, const std::vector<PublicKey>& pks, const std::vector<Signature>& proofs, std::vector<int32_t>* status = nullptr) {
+        const size_t n = pks.size();
+        if (n == 0 || proofs.size() != n) throw Error("BLS::pop_verify: one proof per key", BLSW_ERR_ARG);
+        std::vector<uint8_t> pk(n * 48), pr(n * 96);
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(&pk[48 * i], pks[i].bytes.data(), 48);
+            std::memcpy(&pr[96 * i], proofs[i].bytes.data(), 96);
+        }
+        uint64_t bytes = 0;
+        check(blsw_verify_workspace_bytes(n, 48, &bytes), "blsw_verify_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_pk(pk.size()), d_pr(pr.size()), d_st(n * 8), d_res(n * 4);
+        d_pk.upload(pk.data(), pk.size());
+        d_pr.upload(pr.data(), pr.size());
+        check(blsw_pop_verify_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_pr.get()), n, static_cast<int32_t*>(d_res.get()),
+                                    static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+              "blsw_pop_verify_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n);
+        d_res.download(r.data(), n * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
         }
         std::vector<bool> out(n);
         for (size_t i = 0; i < n; i++) out[i] = r[i] == 1;

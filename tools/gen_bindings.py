@@ -20,7 +20,7 @@ SCALARS = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i3
 STRUCT_NAMES = {"blsw_layout_t": "BlswLayout", "blsw_engine_options_t": "BlswEngineOptions", "blsw_engine_t": "BlswEngine",
                 "blsw_matrices_t": "BlswMatrices", "blsw_matrices_info_t": "BlswMatricesInfo",
                 "blsw_r1cs_t": "BlswR1cs", "blsw_compact_layout_t": "BlswCompactLayout", "blsw_compact_layout_multi_t": "BlswCompactLayoutMulti",
-                "blsw_keyset_t": "BlswKeyset", "blsw_registry_t": "BlswRegistry"}
+                "blsw_keyset_t": "BlswKeyset", "blsw_registry_t": "BlswRegistry", "blsw_dst_t": "BlswDst"}
 
 
 def strip_comments(text):
@@ -85,7 +85,8 @@ def rust_block(h=None):
     out.append("")
     for sname, fields in h["structs"].items():
         has_ptr = any("*" in ctype for ctype, _ in fields)
-        out.append("#[repr(C)] #[derive(%sClone, Copy, Debug)]" % ("" if has_ptr else "Default, "))
+        long_array = any(int(m.group(1)) > 32 for m in (re.search(r"\[(\d+)\]$", ctype) for ctype, _ in fields) if m)  # no Default for [T; N > 32]
+        out.append("#[repr(C)] #[derive(%sClone, Copy, Debug)]" % ("" if has_ptr or long_array else "Default, "))
         out.append("pub struct %s {   // %s: %d fields" % (STRUCT_NAMES[sname], sname, len(fields)))
         line = "   "
         for ctype, f in fields:
