@@ -213,6 +213,10 @@ def lib():
             getattr(L, name + "_dst").argtypes = list(plain[:-1]) + [dp, plain[-1]]
         L.blsw_pop_prove_batch.argtypes = [vp, u64, vp, vp, vp, vp, u64, vp]
         L.blsw_pop_verify_batch.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp]
+        L.blsw_verify_groups_shared_workspace_bytes.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_verify_groups_shared_batch.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, u32, dp, vp, vp, vp, vp, u64, vp]
+        L.blsw_registry_verify_shared_workspace_bytes.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_registry_verify_shared_batch.argtypes = [vp, vp, u64, vp, vp, vp, u32, u64, vp, u64, vp, u32, dp, vp, vp, vp, vp, vp, u64, vp]
         _lib = L
     return _lib
 
@@ -239,7 +243,9 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_r1cs_handle_pair_families", "blsw_r1cs_check_compact_multi", "blsw_r1cs_check_compact_multi_ex", "blsw_r1cs_evaluate_compact_multi",
                     "blsw_registry_bytes", "blsw_registry_create", "blsw_registry_append", "blsw_registry_size", "blsw_registry_key_status", "blsw_registry_destroy",
                     "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch", "blsw_verify_pairs_workspace_bytes", "blsw_verify_pairs_batch",
-                    "blsw_dst_set", "blsw_dst_default", "blsw_dst_pop", "blsw_hash_to_field_batch", "blsw_pop_prove_batch", "blsw_pop_verify_batch"] + [e + "_dst" for e in _DST_ENTRIES]
+                    "blsw_dst_set", "blsw_dst_default", "blsw_dst_pop", "blsw_hash_to_field_batch", "blsw_pop_prove_batch", "blsw_pop_verify_batch",
+                    "blsw_verify_groups_shared_workspace_bytes", "blsw_verify_groups_shared_batch", "blsw_registry_verify_shared_workspace_bytes",
+                    "blsw_registry_verify_shared_batch"] + [e + "_dst" for e in _DST_ENTRIES]
 
 DST_DEFAULT = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # the library's tag: what every value entry hashes under with dst=None
 DST_POP = b"BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # PopProve / PopVerify of the signature draft
@@ -1089,21 +1095,53 @@ def _group_scalars(torch, n, dev):
     return torch.from_numpy(r.view(np.int64)).to(dev)
 
 
-def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
+def _msg_index_rows(torch, msg_index, n, n_msgs):
+    """msg_index [n] of 32-bit integers (int32 storage of the uint32 indices) -> (int64 rows clamped into the table, bool: the index is beyond it)"""
+    assert msg_index.shape == (n,) and msg_index.element_size() == 4 and not msg_index.is_floating_point() and msg_index.is_contiguous()
+    rows = msg_index.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    beyond = rows >= n_msgs
+    return torch.where(beyond, torch.zeros_like(rows), rows), beyond
+
+
+def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None, msg_index=None, want_runs=False):
     """Batch verification of GROUPS of triples with random coefficients (blsw_verify_groups_batch, include/blsw.h): group j is instances
     [j * group, min(n, (j + 1) * group)) and its verdict is 1 iff every instance decodes (both statuses OK), every coefficient is non-zero and
     prod_i e(r_i pk_i, H(m_i)) * e(-g1, sum_i r_i sig_i) == 1 — one final exponentiation per group instead of one per triple. uint8 cuda tensors as
     verify_batch -> int32 [ceil(n / group)], optionally with the decode statuses [n, 2].
     scalars: None draws n 64-bit coefficients from secrets.token_bytes on the host (zeros replaced by 1); a given int64 / uint64 cuda tensor [n] is
-    used as is — predictable coefficients are NOT sound (include/blsw.h, P4). The workspace is allocated per call (the caching allocator keeps it)."""
+    used as is — predictable coefficients are NOT sound (include/blsw.h, P4). The workspace is allocated per call (the caching allocator keeps it).
+    msg_index: None is the call above. A cuda tensor [n] of 32-bit integers makes msg the TABLE [n_msgs, msg_len] and instance i sign row
+    msg_index[i] (blsw_verify_groups_shared_batch): one hash per row, one pair per run of equal adjacent indices of a group — sort each group by
+    index. An index beyond the table is ST_BAD_INDEX in status[i, 0] and fails its group. want_runs (with an index) appends the runs per group,
+    int32 [ceil(n / group)], after the status."""
     torch = _require_cuda()
     n, msg_len = pk48.shape[0], msg.shape[1]
-    assert pk48.shape == (n, 48) and sig96.shape == (n, 96) and msg.shape[0] == n and pk48.is_contiguous() and sig96.is_contiguous() and msg.is_contiguous()
+    assert pk48.shape == (n, 48) and sig96.shape == (n, 96) and (msg.shape[0] == n or msg_index is not None) and pk48.is_contiguous() and sig96.is_contiguous() and msg.is_contiguous()
     dev = pk48.device
+    if msg_index is None and want_runs:
+        raise ValueError("want_runs needs msg_index: without a message table there are no runs")
     if scalars is None:
         scalars = _group_scalars(torch, n, dev)
     assert scalars.shape == (n,) and scalars.element_size() == 8 and not scalars.is_floating_point() and scalars.is_contiguous() and scalars.device == dev
     wb = ctypes.c_uint64(0)
+    if msg_index is not None:
+        n_msgs = msg.shape[0]
+        assert msg_index.shape == (n,) and msg_index.element_size() == 4 and not msg_index.is_floating_point() and msg_index.is_contiguous() and msg_index.device == dev
+        rc = lib().blsw_verify_groups_shared_workspace_bytes(n, n_msgs, msg_len, group, ctypes.byref(wb))
+        if rc:
+            raise BlswError("blsw_verify_groups_shared_workspace_bytes failed: %d" % rc)
+        ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+        res = torch.empty((n + group - 1) // group, dtype=torch.int32, device=dev)
+        runs = torch.empty((n + group - 1) // group, dtype=torch.int32, device=dev) if want_runs else None
+        status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        tag = _dst_struct(dst) if dst is not None else None
+        rc = lib().blsw_verify_groups_shared_batch(pk48.data_ptr(), sig96.data_ptr(), msg.data_ptr() if msg_len else None, msg_len, n_msgs, msg_index.data_ptr(), n, scalars.data_ptr(),
+                                                   group, ctypes.byref(tag) if tag is not None else None, res.data_ptr(), runs.data_ptr() if want_runs else None, status.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            raise BlswError("blsw_verify_groups_shared_batch failed: %d" % rc)
+        extra = ([status] if want_status else []) + ([runs] if want_runs else [])
+        return (res, *extra) if extra else res
     rc = lib().blsw_verify_groups_workspace_bytes(n, msg_len, group, ctypes.byref(wb))
     if rc:
         raise BlswError("blsw_verify_groups_workspace_bytes failed: %d" % rc)
@@ -1117,18 +1155,32 @@ def verify_groups(pk48, msg, sig96, group=64, scalars=None, want_status=False, d
     return (res, status) if want_status else res
 
 
-def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
+def verify_batch_grouped(pk48, msg, sig96, group=64, scalars=None, want_status=False, dst=None, msg_index=None, want_runs=False):
     """verify_batch through verify_groups: int32 [n] with the meaning of verify_batch. The instances of passing groups are 1; the instances of failing
     groups are gathered, put through verify_batch and scattered back. ONE host synchronisation, to learn which groups failed. A batch in which most
-    groups hold a bad instance is slower this way than verify_batch: it pays for the groups and then for nearly the whole batch again."""
+    groups hold a bad instance is slower this way than verify_batch: it pays for the groups and then for nearly the whole batch again.
+    msg_index / want_runs: verify_groups' message table; the failing groups' instances are re-checked on their gathered rows, and an instance whose
+    index lies beyond the table is 0."""
     torch = _require_cuda()
     n = pk48.shape[0]
-    gres, status = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
+    if msg_index is None:
+        if want_runs:
+            raise ValueError("want_runs needs msg_index: without a message table there are no runs")
+        gres, status = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
+        runs = None
+    else:
+        gres, status, runs = verify_groups(pk48, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst, msg_index=msg_index, want_runs=True)
     res = gres.repeat_interleave(group)[:n].contiguous()
     bad = torch.nonzero(res == 0).flatten()  # the synchronisation
     if bad.numel():
-        res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous(), dst=dst)
-    return (res, status) if want_status else res
+        if msg_index is None:
+            res[bad] = verify_batch(pk48[bad].contiguous(), msg[bad].contiguous(), sig96[bad].contiguous(), dst=dst)
+        else:
+            rows, beyond = _msg_index_rows(torch, msg_index, n, msg.shape[0])
+            sub = verify_batch(pk48[bad].contiguous(), msg[rows[bad]].contiguous(), sig96[bad].contiguous(), dst=dst)
+            res[bad] = torch.where(beyond[bad], torch.zeros_like(sub), sub)
+    extra = ([status] if want_status else []) + ([runs] if want_runs else [])
+    return (res, *extra) if extra else res
 
 
 VERIFY_PAIRS_CHUNK = _header_define("BLSW_VPAIRS_CHUNK")  # pairs of one instance that one six-lane team folds with shared squarings
@@ -1289,15 +1341,23 @@ class KeyRegistry:
             pass
 
 
-def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=None, want_status=False, want_aggregate=False, dst=None):
+def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=None, want_status=False, want_aggregate=False, dst=None, msg_index=None, want_runs=False):
     """fast_aggregate_verify as values over a KeyRegistry and n index lists (blsw_registry_verify_batch, include/blsw.h): set i is
     indices[offsets[i]:offsets[i + 1]] — indices a cuda tensor [n_indices] of 32-bit integers (int32 storage of the uint32 indices), offsets [n + 1]
     of 64-bit integers; uint8 cuda tensors msg [n, msg_len], sig96 [n, 96]. A repeated index is added as often as it occurs.
     group == 0 -> int32 [n]: the verdict of fast_aggregate_verify_batch on the gathered keys (an empty list, a bad entry and an identity sum are
     false). group >= 1 -> int32 [ceil(n / group)]: verify_groups' statement over the sets' sums; scalars None draws coefficients as verify_groups does.
     Returns the verdicts, or a tuple of them followed by what was asked for, in this order: status [n, 2] int32 ([i, 0] of the set's key —
-    ST_BAD_INDEX for bad offsets or an index >= registry.size —, [i, 1] of the signature), aggregate [n, 48] uint8."""
+    ST_BAD_INDEX for bad offsets or an index >= registry.size —, [i, 1] of the signature), aggregate [n, 48] uint8, runs.
+    msg_index: None is the call above. A cuda tensor [n] of 32-bit integers makes msg the TABLE [n_msgs, msg_len] and set i sign row msg_index[i].
+    group >= 1 runs blsw_registry_verify_shared_batch (one hash per row, one pair per run of equal adjacent indices of a group: sort each group by
+    index), and want_runs appends the runs per group, int32 [ceil(n / group)]. group == 0 gathers msg[msg_index] and calls the plain entry. In both
+    an index beyond the table is ST_BAD_INDEX in status[i, 0] and false."""
     torch = _require_cuda()
+    if msg_index is None and want_runs:
+        raise ValueError("want_runs needs msg_index: without a message table there are no runs")
+    if msg_index is not None:
+        return _registry_verify_shared(torch, registry, indices, offsets, msg, sig96, group, scalars, want_status, want_aggregate, dst, msg_index, want_runs)
     n, msg_len, n_indices = msg.shape[0], msg.shape[1], indices.shape[0]
     assert indices.dim() == 1 and offsets.shape == (n + 1,) and sig96.shape == (n, 96)
     assert indices.element_size() == 4 and offsets.element_size() == 8 and not indices.is_floating_point() and not offsets.is_floating_point()
@@ -1324,7 +1384,48 @@ def registry_verify(registry, indices, offsets, msg, sig96, group=0, scalars=Non
     return (res, *extra) if extra else res
 
 
-def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, scalars=None, want_status=False, dst=None):
+def _registry_verify_shared(torch, registry, indices, offsets, msg, sig96, group, scalars, want_status, want_aggregate, dst, msg_index, want_runs):
+    """registry_verify over a message table (its docstring has the rules)"""
+    n, n_msgs, msg_len, n_indices, dev = sig96.shape[0], msg.shape[0], msg.shape[1], indices.shape[0], registry.device
+    assert msg_index.shape == (n,) and msg_index.element_size() == 4 and not msg_index.is_floating_point() and msg_index.is_contiguous() and msg_index.device == dev
+    if group == 0:  # nothing is shared per set: a gather and the plain entry, the bad-index rule placed in front here
+        if want_runs:
+            raise ValueError("want_runs needs group >= 1: the per-set form has no runs")
+        rows, beyond = _msg_index_rows(torch, msg_index, n, n_msgs)
+        out = registry_verify(registry, indices, offsets, msg[rows].contiguous(), sig96, want_status=True, want_aggregate=want_aggregate, dst=dst)
+        res, status = out[0], out[1]
+        res = torch.where(beyond, torch.zeros_like(res), res)
+        status[:, 0] = torch.where(beyond, torch.full_like(status[:, 0], ST_BAD_INDEX), status[:, 0])
+        extra = ([status] if want_status else []) + ([out[2]] if want_aggregate else [])
+        return (res, *extra) if extra else res
+    assert indices.dim() == 1 and offsets.shape == (n + 1,) and sig96.shape == (n, 96)
+    assert indices.element_size() == 4 and offsets.element_size() == 8 and not indices.is_floating_point() and not offsets.is_floating_point()
+    assert all(t.is_contiguous() and t.device == dev for t in (indices, offsets, msg, sig96)) and msg.dtype == torch.uint8 and sig96.dtype == torch.uint8
+    if scalars is None:
+        scalars = _group_scalars(torch, n, dev)
+    assert scalars.shape == (n,) and scalars.element_size() == 8 and not scalars.is_floating_point() and scalars.is_contiguous() and scalars.device == dev
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_registry_verify_shared_workspace_bytes(n, n_msgs, msg_len, group, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_registry_verify_shared_workspace_bytes failed: %d" % rc)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    n_groups = (n + group - 1) // group
+    res = torch.empty(n_groups, dtype=torch.int32, device=dev)
+    runs = torch.empty(n_groups, dtype=torch.int32, device=dev) if want_runs else None
+    status = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    agg = torch.empty((n, 48), dtype=torch.uint8, device=dev) if want_aggregate else None
+    tag = _dst_struct(dst) if dst is not None else None
+    rc = lib().blsw_registry_verify_shared_batch(registry._r, indices.data_ptr() if n_indices else None, n_indices, offsets.data_ptr(), sig96.data_ptr(),
+                                                 msg.data_ptr() if msg_len else None, msg_len, n_msgs, msg_index.data_ptr(), n, scalars.data_ptr(), group,
+                                                 ctypes.byref(tag) if tag is not None else None, res.data_ptr(), runs.data_ptr() if want_runs else None, status.data_ptr(),
+                                                 agg.data_ptr() if want_aggregate else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_registry_verify_shared_batch failed: %d" % rc)
+    extra = ([status] if want_status else []) + ([agg] if want_aggregate else []) + ([runs] if want_runs else [])
+    return (res, *extra) if extra else res
+
+
+def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, scalars=None, want_status=False, dst=None, msg_index=None, want_runs=False):
     """registry_verify(group=0)'s per-set verdicts through the grouped form: the sets of passing groups are 1; the sets of failing groups are
     re-checked with the per-set form and scattered back. CSR is one run of n + 1 offsets and the failing sets' lists are not adjacent, so their
     entries are gathered into an index list of their own. ONE host synchronisation: the group verdicts and the n + 1 offsets come to the host in a
@@ -1333,8 +1434,14 @@ def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, sc
     torch = _require_cuda()
     import numpy as np
 
-    n, dev = msg.shape[0], msg.device
-    gres, st = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
+    n, dev = sig96.shape[0], msg.device
+    runs = None
+    if msg_index is None:
+        if want_runs:
+            raise ValueError("want_runs needs msg_index: without a message table there are no runs")
+        gres, st = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst)
+    else:  # the failing groups' sets are re-checked on their gathered rows; a set whose index lies beyond the table stays 0
+        gres, st, runs = registry_verify(registry, indices, offsets, msg, sig96, group=group, scalars=scalars, want_status=True, dst=dst, msg_index=msg_index, want_runs=True)
     res = gres.repeat_interleave(group)[:n].contiguous()
     host = torch.cat([res.to(torch.int64), offsets.view(torch.int64)]).cpu().numpy()  # the synchronisation
     bad = np.flatnonzero(host[:n] == 0)
@@ -1349,8 +1456,12 @@ def registry_verify_grouped(registry, indices, offsets, msg, sig96, group=64, sc
         sub_idx = indices[torch.from_numpy(pos).to(dev)].contiguous()
         sub_off = torch.from_numpy(np.concatenate([np.zeros(1, np.int64), ends])).to(dev)
         bad_t = torch.from_numpy(bad).to(dev)
-        res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg[bad_t].contiguous(), sig96[bad_t].contiguous(), dst=dst)
-    return (res, st) if want_status else res
+        if msg_index is None:
+            res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg[bad_t].contiguous(), sig96[bad_t].contiguous(), dst=dst)
+        else:
+            res[bad_t] = registry_verify(registry, sub_idx, sub_off, msg, sig96[bad_t].contiguous(), dst=dst, msg_index=msg_index[bad_t].contiguous())
+    extra = ([st] if want_status else []) + ([runs] if want_runs else [])
+    return (res, *extra) if extra else res
 
 
 def fast_aggregate_verify_batch(pks48, msg, sig96):

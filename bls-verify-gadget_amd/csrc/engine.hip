@@ -1636,6 +1636,87 @@ int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indic
                                uint64_t workspace_bytes, void* stream_) {
     return blsw_registry_verify_batch_dst(r, d_indices, n_indices, d_offsets, d_sig96, d_msg, msg_len, n, d_scalars, group, d_result, d_status, d_agg48, d_workspace, workspace_bytes, nullptr, stream_);
 }
+// Grouped verification over a message table (include/blsw.h; vshared.hpp). Workspace: the plain grouped layout over n, the run arrays (leader and
+// length per slot, runs per group), the run sums and their flags, then the hash's carve over the n_msgs table rows without the latency buffers.
+struct VerifySharedOffsets {
+    VerifyGroupsOffsets g;
+    uint64_t slot_leader, slot_len, runs, rsum, rflag;
+};
+static uint64_t verify_shared_offsets(uint64_t n, uint32_t group, VerifySharedOffsets* f) {
+    const uint64_t G = (n + group - 1) / group;
+    uint64_t o = verify_groups_offsets(n, group, &f->g);
+    f->slot_leader = o;
+    o = align_up(o + n * sizeof(uint32_t), 256);
+    f->slot_len = o;
+    o = align_up(o + n * sizeof(uint32_t), 256);
+    f->runs = o;
+    o = align_up(o + G * sizeof(uint32_t), 256);
+    f->rsum = o;
+    o = align_up(o + 3 * n * sizeof(Fp), 256);
+    f->rflag = o;
+    return align_up(o + n * sizeof(int32_t), 256);
+}
+static bool shared_shape_ok(uint64_t n, uint64_t n_msgs, uint32_t msg_len, uint32_t group) {
+    return n != 0 && n <= 0x7fffffffu && n_msgs != 0 && n_msgs <= 0x7fffffffu && msg_len <= 65535 && group != 0 && group <= 65535;
+}
+int blsw_verify_groups_shared_workspace_bytes(uint64_t n, uint64_t n_msgs, uint32_t msg_len, uint32_t group, uint64_t* bytes) {
+    if (!bytes || !shared_shape_ok(n, n_msgs, msg_len, group)) return BLSW_ERR_ARG;
+    VerifySharedOffsets f;
+    *bytes = direct_values_bytes(n_msgs, msg_len, verify_shared_offsets(n, group, &f), false);
+    return BLSW_OK;
+}
+int blsw_registry_verify_shared_workspace_bytes(uint64_t n, uint64_t n_msgs, uint32_t msg_len, uint32_t group, uint64_t* bytes) {
+    return blsw_verify_groups_shared_workspace_bytes(n, n_msgs, msg_len, group, bytes);  // the registry's table lives in the handle
+}
+// the stages behind both entries, once the keys (pk_xy, status[i][0]) and the signatures (sig_xy, status[i][1]) are decoded and the table is hashed
+static void launch_shared(const VerifySharedOffsets& f, char* base, const Group& g, uint64_t n, uint64_t n_msgs, const uint32_t* d_msg_index, const uint64_t* d_scalars,
+                          uint32_t group, int32_t* d_group_result, uint32_t* d_group_runs, int32_t* d_status, hipStream_t st) {
+    launch_verify_groups_shared(n, group, BLSW_VGROUP_CHUNK, g.ws, n_msgs, d_msg_index, reinterpret_cast<uint64_t*>(base + f.g.pk), reinterpret_cast<uint64_t*>(base + f.g.sig), d_status,
+                                d_scalars, reinterpret_cast<Fp*>(base + f.g.p_scaled), reinterpret_cast<Fp*>(base + f.g.s_scaled), reinterpret_cast<Fp*>(base + f.g.sum),
+                                reinterpret_cast<int32_t*>(base + f.g.gflag), reinterpret_cast<Fp*>(base + f.g.lines_h), reinterpret_cast<Fp*>(base + f.g.lines_g),
+                                reinterpret_cast<Fp*>(base + f.g.partials), reinterpret_cast<uint32_t*>(base + f.slot_leader), reinterpret_cast<uint32_t*>(base + f.slot_len),
+                                reinterpret_cast<uint32_t*>(base + f.runs), reinterpret_cast<Fp*>(base + f.rsum), reinterpret_cast<int32_t*>(base + f.rflag), d_group_runs,
+                                d_group_result, st);
+}
+int blsw_verify_groups_shared_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msgs, uint32_t msg_len, uint64_t n_msgs, const uint32_t* d_msg_index, uint64_t n,
+                                    const uint64_t* d_scalars, uint32_t group, const blsw_dst_t* dst, int32_t* d_group_result, uint32_t* d_group_runs, int32_t* d_status,
+                                    void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    if (!dst_ok(dst) || !shared_shape_ok(n, n_msgs, msg_len, group) || !d_pk48 || !d_sig96 || (!d_msgs && msg_len) || !d_msg_index || !d_scalars || !d_group_result || !d_status ||
+        !d_workspace)
+        return BLSW_ERR_ARG;
+    VerifySharedOffsets f;
+    const uint64_t off_ws = verify_shared_offsets(n, group, &f);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    Group g;
+    if (int rc = direct_values_group(d_msgs, msg_len, n_msgs, d_workspace, workspace_bytes, off_ws, st, &g, false)) return rc;
+    hipLaunchKernelGGL(k_decode, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, d_pk48, d_sig96, n, reinterpret_cast<uint64_t*>(base + f.g.pk),
+                       reinterpret_cast<uint64_t*>(base + f.g.sig), d_status);
+    launch_values_hash(g, st, dst);
+    launch_shared(f, base, g, n, n_msgs, d_msg_index, d_scalars, group, d_group_result, d_group_runs, d_status, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_registry_verify_shared_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96, const uint8_t* d_msgs,
+                                      uint32_t msg_len, uint64_t n_msgs, const uint32_t* d_msg_index, uint64_t n, const uint64_t* d_scalars, uint32_t group, const blsw_dst_t* dst,
+                                      int32_t* d_group_result, uint32_t* d_group_runs, int32_t* d_status, uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes,
+                                      void* stream_) {
+    if (!dst_ok(dst) || !shared_shape_ok(n, n_msgs, msg_len, group) || !d_sig96 || (!d_msgs && msg_len) || !d_msg_index || !d_scalars || !d_group_result || !d_status || !d_workspace || !r ||
+        !d_offsets || (!d_indices && n_indices) || n_indices > (1ull << 40) || r->size == 0)
+        return BLSW_ERR_ARG;
+    VerifySharedOffsets f;
+    const uint64_t off_ws = verify_shared_offsets(n, group, &f);
+    char* base = reinterpret_cast<char*>(d_workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(r->device);
+    Group g;
+    if (int rc = direct_values_group(d_msgs, msg_len, n_msgs, d_workspace, workspace_bytes, off_ws, st, &g, false)) return rc;
+    launch_committee_decode(nullptr, 0, d_sig96, n, nullptr, nullptr, reinterpret_cast<uint64_t*>(base + f.g.sig), d_status, st);  // the n signature lanes alone, status[i][1]
+    launch_registry_sum(r->records, r->size, d_indices, n_indices, d_offsets, n, reinterpret_cast<uint64_t*>(base + f.g.pk), d_status, d_agg48, st);
+    launch_values_hash(g, st, dst);
+    launch_shared(f, base, g, n, n_msgs, d_msg_index, d_scalars, group, d_group_result, d_group_runs, d_status, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
 // BLS::sign + PublicKey::from(&sk) for a batch (bls.rs:411-425, 183-195). Workspace: blsw_hash_to_g2_workspace_bytes.
 int blsw_sign_batch_dst(const uint8_t* d_sk32_le, const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint8_t* d_sig96, uint64_t* d_sig_xy, uint8_t* d_pk48,
                         uint64_t* d_pk_xy, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, const blsw_dst_t* dst, void* stream_) {

@@ -848,6 +848,14 @@ void launch_verify_values(uint64_t n, const Workspace& ws, const uint64_t* pk_xy
 // (k_vgroups.hip, vgroups.hpp). `chunk` <= 31 pairs per team.
 void launch_verify_groups(uint64_t n, uint32_t group, uint32_t chunk, const Workspace& ws, const uint64_t* pk_xy, const uint64_t* sig_xy, const int32_t* status, const uint64_t* scalars,
                           Fp* p_scaled, Fp* s_scaled, Fp* sum_xy, int32_t* gflag, Fp* lines_h, Fp* lines_g, Fp* partials, int32_t* result, hipStream_t st);
+// blsw_verify_groups_shared_batch: the same over a message table (k_vgroups.hip, vshared.hpp). msg_index [n] names each instance's row of the table
+// that ws hashed (n_msgs rows); an index beyond it becomes DEC_BAD_COUNT in status[i][0]. Instances of a group with equal adjacent indices form a
+// run: one key sum (rsum [3][n], rflag [n], by compact slot), one line chain and one pair of the fold. slot_leader, slot_len [n], runs [n_groups];
+// runs_out (nullable) receives the groups' run counts.
+void launch_verify_groups_shared(uint64_t n, uint32_t group, uint32_t chunk, const Workspace& ws, uint64_t n_msgs, const uint32_t* msg_index, const uint64_t* pk_xy,
+                                 const uint64_t* sig_xy, int32_t* status, const uint64_t* scalars, Fp* p_scaled, Fp* s_scaled, Fp* sum_xy, int32_t* gflag, Fp* lines_h, Fp* lines_g,
+                                 Fp* partials, uint32_t* slot_leader, uint32_t* slot_len, uint32_t* runs, Fp* rsum, int32_t* rflag, uint32_t* runs_out, int32_t* result,
+                                 hipStream_t st);
 // blsw_verify_pairs_batch: decode of n * n_pairs keys and n signatures, the instances' statuses, one line chain per used pair and per signature,
 // chunked fold, one final exponentiation per instance (k_vpairs.hip, vpairs.hpp). `chunk` <= 31 pairs per team; ws holds the hash of the n * n_pairs messages.
 void launch_verify_pairs(uint64_t n, uint32_t n_pairs, uint32_t chunk, const Workspace& ws, const uint8_t* pks48, const uint8_t* sig96, const uint32_t* counts, Fp* key_xy,

@@ -882,6 +882,53 @@ int blsw_pop_prove_batch(const uint8_t* d_sk32_le, uint64_t n, uint8_t* d_proof9
 int blsw_pop_verify_batch(const uint8_t* d_pk48, const uint8_t* d_proof96, uint64_t n, int32_t* d_result, int32_t* d_status, void* d_workspace,
                           uint64_t workspace_bytes, void* stream);
 
+/* GROUPED VERIFICATION OVER A MESSAGE TABLE: hash once, one pair per run. New symbols only: the ABI number stays 17 and blsw_engine_options_t is
+ * untouched. Many signature sets of a consensus client sign the same message; with blsw_verify_groups_batch or blsw_registry_verify_batch
+ * (group >= 1) the caller materialises it n times and the library hashes it, walks its 68 line steps and folds its pair n times. Within a group
+ *     prod_{i, m_i = m} e(r_i pk_i, H(m)) = e(sum_i r_i pk_i, H(m)),
+ * so the two entries below take the messages as a table with one index per instance and spend one hash per table row and one line chain and one
+ * pair per RUN of equal indices.
+ *   d_msgs [n_msgs][msg_len]: the table. d_msg_index [n] uint32: instance i signs row d_msg_index[i].
+ *   dst: nullable, as in the *_dst entries: NULL is the library's tag and its kernel. There is no second pair of symbols.
+ *   Both entries are grouped only: group >= 1 and d_scalars are required (the per-set form gains nothing a gather does not give it). The groups
+ *   are exactly those of blsw_verify_groups_batch: instances [g * group, min(n, (g + 1) * group)).
+ *   RUNS. Instance i starts a run iff it is the first instance of its group or d_msg_index[i] != d_msg_index[i - 1]; a run is its leader and the
+ *   instances up to the next leader or the end of the group. This is a function of (n, group, d_msg_index) alone: statuses and scalars play no
+ *   part, and equality is of indices, not of message bytes. Equal indices that are not adjacent are separate runs, which costs time, never
+ *   correctness: SORT EACH GROUP BY INDEX.
+ *   VERDICT. With P_i = r_i pk_i (the identity for an excluded instance, as in blsw_verify_groups_batch) and R = sum_{i in run} P_i,
+ *     d_group_result[g] = 1  iff  every instance of g is included, and  prod_{runs of g} e(R_run, H(d_msgs[idx_run])) * e(-g1, S_g) == 1.
+ *   A run whose R is the identity is a skipped pair (factor 1), never zero lines folded in: the rule of an identity S_g.
+ *   d_group_runs [ceil(n / group)] uint32 (nullable): the number of runs of each group.
+ *   d_status [n][2]: what blsw_verify_groups_batch (respectively blsw_registry_verify_batch) writes, with one rule in front: if
+ *   d_msg_index[i] >= n_msgs then [i][0] = BLSW_ST_BAD_INDEX, the instance is excluded, its group is 0 and no table row is read for it.
+ *   Every table row is hashed, whether any instance uses it or not.
+ * What callers can rest on:
+ *   S1. For every input, valid or not, and every choice of scalars, d_group_result and d_status are those of the plain grouped entry on
+ *       d_msg[i] = d_msgs[d_msg_index[i]] with the same scalars (all indices in range): the two compute the same element of GT. P1-P4 carry over.
+ *   S2. The verdict is invariant under a permutation of the instances of a group (with their scalars and indices); only d_group_runs changes.
+ *   S3. d_group_runs is the function stated above.   S4. d_msg_index[i] = i, n_msgs = n: one run per instance.
+ * BLSW_ERR_ARG, before any HIP call and with nothing written: the plain grouped entry's conditions (group == 0 included), n_msgs == 0 or
+ * > 0x7fffffff, d_msg_index == NULL, a non-NULL dst of length 0, d_msgs == NULL with msg_len != 0. BLSW_ERR_WORKSPACE below the size function,
+ * which lays out the plain grouped form over n (points, scaled points, one set of line rows per instance SLOT — the host does not know the runs —
+ * group lines, partials), the run arrays (three words per instance, one per group), the run sums (three field elements per slot) and the hash's
+ * carve over n_msgs rows, not n, without the latency kernels' buffers (as blsw_verify_pairs_batch). It is non-decreasing in n, n_msgs and msg_len;
+ * in `group` it follows the plain layout, whose per-group rows shrink as groups grow.
+ * What stays out: the committee form (one committee, a message per slot, nothing shared); blsw_verify_pairs_batch (its pairs belong to one
+ * signature and carry no coefficients); merging repeats that are not adjacent (a sort inside the call); a caller's bound on the number of runs
+ * that would shrink the line rows. */
+int blsw_verify_groups_shared_workspace_bytes(uint64_t n, uint64_t n_msgs, uint32_t msg_len, uint32_t group, uint64_t* bytes);
+int blsw_verify_groups_shared_batch(const uint8_t* d_pk48, const uint8_t* d_sig96, const uint8_t* d_msgs, uint32_t msg_len, uint64_t n_msgs,
+                                    const uint32_t* d_msg_index, uint64_t n, const uint64_t* d_scalars, uint32_t group, const blsw_dst_t* dst,
+                                    int32_t* d_group_result, uint32_t* d_group_runs, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes,
+                                    void* stream);
+int blsw_registry_verify_shared_workspace_bytes(uint64_t n, uint64_t n_msgs, uint32_t msg_len, uint32_t group, uint64_t* bytes);
+int blsw_registry_verify_shared_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets,
+                                      const uint8_t* d_sig96, const uint8_t* d_msgs, uint32_t msg_len, uint64_t n_msgs, const uint32_t* d_msg_index,
+                                      uint64_t n, const uint64_t* d_scalars, uint32_t group, const blsw_dst_t* dst, int32_t* d_group_result,
+                                      uint32_t* d_group_runs, int32_t* d_status, uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes,
+                                      void* stream);
+
 /* Device micro-benchmarks that give the VALU roofline its MEASURED denominator:
  * which = 0: v_mad_u64_u32 rate (32x32+64 multiply-adds per second, all CUs); 1: Fp Montgomery products per second;
  * 2: Fp inversions (safegcd) per second; 3: Fp products per second inside witness-emitting Fp2 mul + sqr;

@@ -1014,6 +1014,56 @@ struct BLS {
         for (size_t j = 0; j < n_groups; j++) out[j] = r[j] == 1;
         return out;
     }
+    // verify_groups over a message TABLE (blsw_verify_groups_shared_batch, include/blsw.h): triple i signs table[msg_index[i]]. One hash per table row
+    // and one pair per run of equal adjacent indices of a group — sort each group by index. An index beyond the table is BLSW_ST_BAD_INDEX in
+    // status[2 i] and fails its group. runs (when given) receives the number of runs of each group; everything else as verify_groups.
+    static std::vector<bool> verify_groups_shared(const Parameters&, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& table,
+                                                  const std::vector<uint32_t>& msg_index, const std::vector<Signature>& sigs, uint32_t group = 64,
+                                                  std::vector<uint64_t> scalars = {}, std::vector<int32_t>* status = nullptr, std::vector<uint32_t>* runs = nullptr,
+                                                  const Dst& dst = Dst()) {
+        const size_t n = pks.size(), n_msgs = table.size();
+        if (n == 0 || n_msgs == 0 || msg_index.size() != n || sigs.size() != n || group == 0)
+            throw Error("BLS::verify_groups_shared: a table, and one index and one signature per key", BLSW_ERR_ARG);
+        if (scalars.empty()) scalars = group_scalars(n);
+        if (scalars.size() != n) throw Error("BLS::verify_groups_shared: one coefficient per triple", BLSW_ERR_ARG);
+        const uint32_t msg_len = (uint32_t)table[0].size();
+        std::vector<uint8_t> pk(n * 48), sg(n * 96), msg(n_msgs * (size_t)msg_len);
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(&pk[48 * i], pks[i].bytes.data(), 48);
+            std::memcpy(&sg[96 * i], sigs[i].bytes.data(), 96);
+        }
+        for (size_t r = 0; r < n_msgs; r++) {
+            if (table[r].size() != msg_len) throw Error("BLS::verify_groups_shared: messages of one length per table", BLSW_ERR_ARG);
+            if (msg_len) std::memcpy(&msg[(size_t)msg_len * r], table[r].data(), msg_len);
+        }
+        const size_t n_groups = (n + group - 1) / group;
+        uint64_t bytes = 0;
+        check(blsw_verify_groups_shared_workspace_bytes(n, n_msgs, msg_len, group, &bytes), "blsw_verify_groups_shared_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_pk(pk.size()), d_sg(sg.size()), d_msg(msg.size()), d_ix(n * 4), d_sc(n * 8), d_st(n * 8), d_res(n_groups * 4), d_runs(n_groups * 4);
+        d_pk.upload(pk.data(), pk.size());
+        d_sg.upload(sg.data(), sg.size());
+        d_ix.upload(msg_index.data(), n * 4);
+        d_sc.upload(scalars.data(), n * 8);
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        check(blsw_verify_groups_shared_batch(static_cast<const uint8_t*>(d_pk.get()), static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n_msgs,
+                                              static_cast<const uint32_t*>(d_ix.get()), n, static_cast<const uint64_t*>(d_sc.get()), group, dst.get(),
+                                              static_cast<int32_t*>(d_res.get()), static_cast<uint32_t*>(d_runs.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+              "blsw_verify_groups_shared_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n_groups);
+        d_res.download(r.data(), n_groups * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
+        }
+        if (runs) {
+            runs->resize(n_groups);
+            d_runs.download(runs->data(), n_groups * 4);
+        }
+        std::vector<bool> out(n_groups);
+        for (size_t j = 0; j < n_groups; j++) out[j] = r[j] == 1;
+        return out;
+    }
     // BLS::verify through verify_groups: the triples of passing groups are true, those of failing groups go through verify once more. A batch in which
     // most groups hold a bad triple is slower this way than verify.
     static std::vector<bool> verify_grouped(const Parameters& params, const std::vector<PublicKey>& pks, const std::vector<std::vector<uint8_t>>& messages,
@@ -1186,6 +1236,70 @@ struct BLS {
         }
         std::vector<bool> out(n_res);
         for (size_t j = 0; j < n_res; j++) out[j] = r[j] == 1;
+        return out;
+    }
+    // fast_aggregate_verify_indexed (group >= 1) over a message TABLE (blsw_registry_verify_shared_batch, include/blsw.h): set i signs
+    // table[msg_index[i]]; one hash per table row, one pair per run of equal adjacent indices of a group — sort each group by index. An index beyond
+    // the table is BLSW_ST_BAD_INDEX in status[2 i], in front of the registry's own rules. runs (when given) receives the runs of each group.
+    static std::vector<bool> fast_aggregate_verify_indexed_shared(const Parameters&, const KeyRegistry& registry, const std::vector<std::vector<uint32_t>>& index_lists,
+                                                                  const std::vector<std::vector<uint8_t>>& table, const std::vector<uint32_t>& msg_index,
+                                                                  const std::vector<Signature>& sigs, uint32_t group = 64, std::vector<uint64_t> scalars = {},
+                                                                  std::vector<int32_t>* status = nullptr, std::vector<PublicKey>* aggregates = nullptr,
+                                                                  std::vector<uint32_t>* runs = nullptr, const Dst& dst = Dst()) {
+        const size_t n = index_lists.size(), n_msgs = table.size();
+        if (n == 0 || n_msgs == 0 || msg_index.size() != n || sigs.size() != n || group == 0)
+            throw Error("BLS::fast_aggregate_verify_indexed_shared: a table, and one index list, message index and signature per set", BLSW_ERR_ARG);
+        if (scalars.empty()) scalars = group_scalars(n);
+        if (scalars.size() != n) throw Error("BLS::fast_aggregate_verify_indexed_shared: one coefficient per set", BLSW_ERR_ARG);
+        const uint32_t msg_len = (uint32_t)table[0].size();
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) off[i + 1] = off[i] + index_lists[i].size();
+        std::vector<uint32_t> idx(off[n]);
+        std::vector<uint8_t> sg(n * 96), msg(n_msgs * (size_t)msg_len);
+        for (size_t i = 0; i < n; i++) {
+            if (!index_lists[i].empty()) std::memcpy(&idx[off[i]], index_lists[i].data(), index_lists[i].size() * 4);
+            std::memcpy(&sg[96 * i], sigs[i].bytes.data(), 96);
+        }
+        for (size_t r = 0; r < n_msgs; r++) {
+            if (table[r].size() != msg_len) throw Error("BLS::fast_aggregate_verify_indexed_shared: messages of one length per table", BLSW_ERR_ARG);
+            if (msg_len) std::memcpy(&msg[(size_t)msg_len * r], table[r].data(), msg_len);
+        }
+        const size_t n_groups = (n + group - 1) / group;
+        uint64_t bytes = 0;
+        check(blsw_registry_verify_shared_workspace_bytes(n, n_msgs, msg_len, group, &bytes), "blsw_registry_verify_shared_workspace_bytes");
+        detail::DeviceBytes ws(bytes), d_idx(idx.size() * 4), d_off(off.size() * 8), d_sg(sg.size()), d_msg(msg.size()), d_ix(n * 4), d_sc(n * 8), d_st(n * 8), d_agg(n * 48),
+            d_res(n_groups * 4), d_runs(n_groups * 4);
+        if (!idx.empty()) d_idx.upload(idx.data(), idx.size() * 4);
+        d_off.upload(off.data(), off.size() * 8);
+        d_sg.upload(sg.data(), sg.size());
+        d_ix.upload(msg_index.data(), n * 4);
+        d_sc.upload(scalars.data(), n * 8);
+        if (!msg.empty()) d_msg.upload(msg.data(), msg.size());
+        check(blsw_registry_verify_shared_batch(registry.get(), idx.empty() ? nullptr : static_cast<const uint32_t*>(d_idx.get()), idx.size(), static_cast<const uint64_t*>(d_off.get()),
+                                                static_cast<const uint8_t*>(d_sg.get()), static_cast<const uint8_t*>(d_msg.get()), msg_len, n_msgs,
+                                                static_cast<const uint32_t*>(d_ix.get()), n, static_cast<const uint64_t*>(d_sc.get()), group, dst.get(),
+                                                static_cast<int32_t*>(d_res.get()), static_cast<uint32_t*>(d_runs.get()), static_cast<int32_t*>(d_st.get()),
+                                                static_cast<uint8_t*>(d_agg.get()), ws.get(), bytes, nullptr),
+              "blsw_registry_verify_shared_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> r(n_groups);
+        d_res.download(r.data(), n_groups * 4);
+        if (status) {
+            status->resize(2 * n);
+            d_st.download(status->data(), n * 8);
+        }
+        if (aggregates) {
+            std::vector<uint8_t> a(n * 48);
+            d_agg.download(a.data(), a.size());
+            aggregates->resize(n);
+            for (size_t i = 0; i < n; i++) std::memcpy((*aggregates)[i].bytes.data(), &a[48 * i], 48);
+        }
+        if (runs) {
+            runs->resize(n_groups);
+            d_runs.download(runs->data(), n_groups * 4);
+        }
+        std::vector<bool> out(n_groups);
+        for (size_t j = 0; j < n_groups; j++) out[j] = r[j] == 1;
         return out;
     }
     // the per-set verdicts through groups: the sets of passing groups are true, those of failing groups go through the per-set form once more (the
