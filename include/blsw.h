@@ -100,6 +100,7 @@ int blsw_layout_aggregate_inputs(uint32_t msg_len, uint32_t n_keys, uint32_t agg
 int blsw_aggregate_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t n_keys, uint64_t* bytes);
 /* BlsSignatureVerifyGadget::aggregate_verify for n independent instances of n_keys keys each (same message per instance):
  *   d_pks_xy [n][n_keys][12] u64, d_bitmap [n][n_keys] bytes (0/1: Boolean::new_witness), d_sig_xy [n][24], d_msg [n][msg_len]
+ *     (an empty selection and sums that reach the identity are defined inputs; a final sum of O fails the enforced pk != 0 row: tests/test_agg_edges_gpu.py)
  *   d_witness [n][witness_stride] (may be NULL), d_result [n] int32 (the Boolean), d_count [n] uint32 (the UInt32 count)
  * Direct mode, asynchronous on `stream`. */
 int blsw_aggregate_verify_batch(const uint64_t* d_pks_xy, const uint8_t* d_bitmap, uint32_t n_keys, const uint64_t* d_sig_xy, const uint8_t* d_msg,

@@ -17,6 +17,7 @@ from tests import agg_inputs_lib as A
 from tests import chain_edges as E
 from tests import curve_ref as C
 from tests import synth
+from tests.edges_gpu_lib import same, to_dev
 
 pytestmark = pytest.mark.gpu
 N = 70
@@ -85,18 +86,6 @@ def expected(oracle, torch, kind, *args):
             extra = None
         _EXPECT[key] = (res, torch.from_numpy(w.view(np.int64)).cuda(), extra)
     return _EXPECT[key]
-
-
-def same(torch, tag, lane, got, want):
-    assert tuple(got.shape) == tuple(want.shape), (tag, lane, got.shape, want.shape)
-    if not torch.equal(got, want):
-        idx = int(torch.nonzero((got != want).any(dim=1))[0].item())
-        raise AssertionError("%s, lane %d: first mismatching witness index %d" % (tag, lane, idx))
-
-
-def to_dev(torch, a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
 
 
 def run_single(pkg, oracle, tag, max_steps=2, io=False, **options):
