@@ -150,6 +150,10 @@ def lib():
         L.blsw_decode_batch.argtypes = [vp, vp, u64, vp, vp, vp, vp]
         L.blsw_aggregate_points_workspace_bytes.argtypes = [u32, u64, u32, ctypes.POINTER(u64)]
         L.blsw_aggregate_points_batch.argtypes = [u32, vp, u32, u64, vp, vp, vp, u64, vp]
+        L.blsw_combine_points_workspace_bytes.argtypes = [u32, u64, u32, ctypes.POINTER(u64)]
+        L.blsw_combine_points_batch.argtypes = [u32, vp, vp, vp, u32, u64, vp, vp, vp, vp, u64, vp]
+        L.blsw_lagrange_batch.argtypes = [vp, vp, u32, u64, vp, vp, vp]
+        L.blsw_recover_points_batch.argtypes = [u32, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
         L.blsw_sign_batch.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, u64, vp]
         L.blsw_verify_workspace_bytes.argtypes = [u64, u32, ctypes.POINTER(u64)]
         L.blsw_verify_batch.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
@@ -245,7 +249,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_registry_verify_workspace_bytes", "blsw_registry_verify_batch", "blsw_verify_pairs_workspace_bytes", "blsw_verify_pairs_batch",
                     "blsw_dst_set", "blsw_dst_default", "blsw_dst_pop", "blsw_hash_to_field_batch", "blsw_pop_prove_batch", "blsw_pop_verify_batch",
                     "blsw_verify_groups_shared_workspace_bytes", "blsw_verify_groups_shared_batch", "blsw_registry_verify_shared_workspace_bytes",
-                    "blsw_registry_verify_shared_batch"] + [e + "_dst" for e in _DST_ENTRIES]
+                    "blsw_registry_verify_shared_batch", "blsw_combine_points_workspace_bytes", "blsw_combine_points_batch", "blsw_lagrange_batch",
+                    "blsw_recover_points_batch"] + [e + "_dst" for e in _DST_ENTRIES]
 
 DST_DEFAULT = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # the library's tag: what every value entry hashes under with dst=None
 DST_POP = b"BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # PopProve / PopVerify of the signature draft
@@ -1040,6 +1045,94 @@ def aggregate_signatures(sig96):
 
 def aggregate_public_keys(pk48):
     return aggregate_points(1, pk48)
+
+
+ST_BAD_ID = 7  # include/blsw.h: BLSW_ST_BAD_ID, an id that is zero or equal to another id of its list
+
+
+def _combine_shapes(torch, group, points, rows, counts):
+    """the checks combine_points and recover_points share -> (n, k, bytes per point, device)"""
+    nbytes = {1: 48, 2: 96}[group]
+    n, k = points.shape[0], points.shape[1]
+    assert points.shape == (n, k, nbytes) and rows.shape == (n, k, 32) and n > 0 and k > 0
+    assert all(t.dtype == torch.uint8 and t.is_contiguous() for t in (points, rows)) and rows.device == points.device
+    if counts is not None:
+        assert counts.shape == (n,) and counts.element_size() == 4 and not counts.is_floating_point() and counts.is_contiguous() and counts.device == points.device
+    return n, k, nbytes, points.device
+
+
+def _combine_workspace(torch, what, group, n, k, dev):
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_combine_points_workspace_bytes(group, n, k, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_combine_points_workspace_bytes failed: %d" % rc)
+    check_capacity(dev, "%s (n = %d, %d terms each)" % (what, n, k), wb.value)
+    return torch.empty(wb.value, dtype=torch.uint8, device=dev)
+
+
+def combine_points(group, points, scalars, counts=None, want_term_status=False):
+    """sum_j s_j * P_j for n lists of k terms (blsw_combine_points_batch, include/blsw.h): group 1 = public keys ([n, k, 48] uint8), group 2 =
+    signatures ([n, k, 96]); scalars [n, k, 32] uint8, little-endian, below r, PUBLIC (the ladders are not constant-time); counts None or an int32 /
+    uint32 cuda tensor [n]: list i uses its first counts[i] terms. -> (sum [n, 48 | 96] uint8 — zeros for a failing list, the infinity encoding for a
+    sum that is the identity —, status [n] int32[, term_status [n, k, 2] int32: every term's point and scalar decode status])."""
+    torch = _require_cuda()
+    n, k, nbytes, dev = _combine_shapes(torch, group, points, scalars, counts)
+    ws = _combine_workspace(torch, "combine_points", group, n, k, dev)
+    out = torch.empty((n, nbytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    term_status = torch.empty((n, k, 2), dtype=torch.int32, device=dev) if want_term_status else None
+    rc = lib().blsw_combine_points_batch(group, points.data_ptr(), scalars.data_ptr(), counts.data_ptr() if counts is not None else None, k, n, out.data_ptr(),
+                                         status.data_ptr(), term_status.data_ptr() if want_term_status else None, ws.data_ptr(), ws.numel(),
+                                         torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_combine_points_batch failed: %d" % rc)
+    torch.cuda.synchronize(dev)
+    return (out, status, term_status) if want_term_status else (out, status)
+
+
+def lagrange_coefficients(ids, counts=None):
+    """Lagrange coefficients at 0 (blsw_lagrange_batch): ids [n, k, 32] uint8 cuda, little-endian elements of Fr, non-zero and distinct within a list's
+    used ids -> (coeff [n, k, 32] uint8, status [n] int32: ST_OK, ST_BAD_INDEX, ST_IDENTITY (no id), ST_BAD_ENCODING (an id >= r) or ST_BAD_ID). Rows
+    beyond a count and every row of a failing list are zeros."""
+    torch = _require_cuda()
+    n, k = ids.shape[0], ids.shape[1]
+    assert ids.shape == (n, k, 32) and ids.dtype == torch.uint8 and ids.is_contiguous() and n > 0 and k > 0
+    dev = ids.device
+    if counts is not None:
+        assert counts.shape == (n,) and counts.element_size() == 4 and not counts.is_floating_point() and counts.is_contiguous() and counts.device == dev
+    coeff = torch.empty((n, k, 32), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib().blsw_lagrange_batch(ids.data_ptr(), counts.data_ptr() if counts is not None else None, k, n, coeff.data_ptr(), status.data_ptr(),
+                                   torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_lagrange_batch failed: %d" % rc)
+    torch.cuda.synchronize(dev)
+    return coeff, status
+
+
+def recover_points(group, ids, points, counts=None):
+    """sum_j lambda_j(ids) * P_j (blsw_recover_points_batch): threshold recovery from shares at `ids` -> (sum [n, 48 | 96] uint8, status [n] int32)"""
+    torch = _require_cuda()
+    n, k, nbytes, dev = _combine_shapes(torch, group, points, ids, counts)
+    ws = _combine_workspace(torch, "recover_points", group, n, k, dev)
+    out = torch.empty((n, nbytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib().blsw_recover_points_batch(group, points.data_ptr(), ids.data_ptr(), counts.data_ptr() if counts is not None else None, k, n, out.data_ptr(), status.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_recover_points_batch failed: %d" % rc)
+    torch.cuda.synchronize(dev)
+    return out, status
+
+
+def recover_signature(ids, sig96, counts=None):
+    """the group signature from partial signatures [n, k, 96] of the shares at ids [n, k, 32]"""
+    return recover_points(2, ids, sig96, counts)
+
+
+def recover_public_key(ids, pk48, counts=None):
+    """the group public key from share keys [n, k, 48] of the shares at ids [n, k, 32]"""
+    return recover_points(1, ids, pk48, counts)
 
 
 _VERIFY_WS = {}

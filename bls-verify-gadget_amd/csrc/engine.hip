@@ -1955,6 +1955,60 @@ int blsw_aggregate_points_batch(uint32_t group, const uint8_t* d_in, uint32_t k,
     hipLaunchKernelGGL(k_sum_points, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, group, (const Fp*)xy, (const int32_t*)pst, k, n, d_out, d_status);
     return hip_ok(hipGetLastError(), "launch");
 }
+// sum_j s_j P_j and threshold recovery (k_combine.hip, vcombine.hpp). The workspace, each part 256-byte aligned: the decoded points, their
+// statuses, the scaled points (G2: 16 parked Jacobian points per term), and for recover the coefficients and the lists' Lagrange statuses.
+struct CombineCarve {
+    Fp* xy;
+    int32_t* pst;
+    Fp* scaled;
+    uint8_t* coeff;
+    int32_t* lag;
+    uint64_t bytes;
+};
+static CombineCarve carve_combine(uint32_t group, uint64_t n, uint32_t k, char* base) {
+    const uint64_t m = n * k;
+    const uint64_t part[5] = {m * (group == 1 ? 2 : 4) * sizeof(Fp), m * sizeof(int32_t), m * (group == 1 ? 3 : 96) * sizeof(Fp), m * 32, n * sizeof(int32_t)};
+    uint64_t off[6] = {0};
+    for (int i = 0; i < 5; i++) off[i + 1] = off[i] + align_up(part[i], 256);
+    return {reinterpret_cast<Fp*>(base + off[0]), reinterpret_cast<int32_t*>(base + off[1]), reinterpret_cast<Fp*>(base + off[2]), reinterpret_cast<uint8_t*>(base + off[3]),
+            reinterpret_cast<int32_t*>(base + off[4]), off[5]};
+}
+static bool combine_shape_ok(uint64_t n, uint32_t k) { return n != 0 && k != 0 && k <= 65535 && n <= 0x3fffffffu / k; }
+int blsw_combine_points_workspace_bytes(uint32_t group, uint64_t n, uint32_t k, uint64_t* bytes) {
+    if (!bytes || (group != 1 && group != 2) || !combine_shape_ok(n, k)) return BLSW_ERR_ARG;
+    *bytes = carve_combine(group, n, k, nullptr).bytes;
+    return BLSW_OK;
+}
+int blsw_combine_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_scalars32_le, const uint32_t* d_counts, uint32_t k, uint64_t n, uint8_t* d_out,
+                              int32_t* d_status, int32_t* d_term_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    uint64_t need = 0;
+    if (!d_in || !d_scalars32_le || !d_out || !d_status || !d_workspace || blsw_combine_points_workspace_bytes(group, n, k, &need)) return BLSW_ERR_ARG;
+    if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    const CombineCarve c = carve_combine(group, n, k, reinterpret_cast<char*>(d_workspace));
+    launch_combine({group, k, n, d_counts, c.xy, c.pst, d_scalars32_le, nullptr, c.scaled, d_term_status, d_out, d_status}, d_in, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_lagrange_batch(const uint8_t* d_ids32_le, const uint32_t* d_counts, uint32_t k, uint64_t n, uint8_t* d_coeff32_le, int32_t* d_status, void* stream_) {
+    if (!d_ids32_le || !d_coeff32_le || !d_status || !combine_shape_ok(n, k)) return BLSW_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    launch_lagrange(d_ids32_le, d_counts, k, n, d_coeff32_le, d_status, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+int blsw_recover_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_ids32_le, const uint32_t* d_counts, uint32_t k, uint64_t n, uint8_t* d_out,
+                              int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    uint64_t need = 0;
+    if (!d_in || !d_ids32_le || !d_out || !d_status || !d_workspace || blsw_combine_points_workspace_bytes(group, n, k, &need)) return BLSW_ERR_ARG;
+    if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    const CombineCarve c = carve_combine(group, n, k, reinterpret_cast<char*>(d_workspace));
+    launch_lagrange(d_ids32_le, d_counts, k, n, c.coeff, c.lag, st);
+    launch_combine({group, k, n, d_counts, c.xy, c.pst, c.coeff, c.lag, c.scaled, nullptr, d_out, d_status}, d_in, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
 int blsw_hash_to_g2_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes) {
     if (!bytes || n == 0 || msg_len > 65535) return BLSW_ERR_ARG;
     *bytes = direct_values_bytes(n, msg_len, 256);

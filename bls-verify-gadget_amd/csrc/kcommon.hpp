@@ -871,6 +871,24 @@ void launch_committee_sum(const uint8_t* bitmap, uint32_t n_keys, uint64_t n, co
 void launch_registry_append(const uint8_t* pks48, uint32_t first, uint32_t count, void* records, int32_t* key_status, hipStream_t st);
 void launch_registry_sum(const void* records, uint32_t size, const uint32_t* indices, uint64_t n_indices, const uint64_t* offsets, uint64_t n, uint64_t* pk_xy, int32_t* status,
                          uint8_t* agg48, hipStream_t st);
+// blsw_combine_points_batch / blsw_recover_points_batch (k_combine.hip, vcombine.hpp): n lists of k (point, scalar) terms, m = n k
+struct CombineArgs {
+    uint32_t group, k;
+    uint64_t n;
+    const uint32_t* counts;  // [n], nullable: every list uses all k
+    const Fp* xy;            // [m][2 | 4] decoded points (k_decode_points)
+    const int32_t* pst;      // [m] their decode statuses
+    const uint8_t* scalars;  // [m][32] little-endian
+    const int32_t* lag;      // [n] the lists' statuses from launch_lagrange (recover), or nullptr
+    Fp* scaled;              // G1: [3][m] Jacobian; G2: [16 * 6][m], slot 0 the scaled point, slots 1..15 the ladder's table
+    int32_t* term_status;    // [m][2], nullable
+    uint8_t* out;            // [n][48 | 96]
+    int32_t* status;         // [n]
+};
+// decode of `in`, the lists' statuses, scale, sum
+void launch_combine(const CombineArgs& a, const uint8_t* in, hipStream_t st);
+// coeff [n][k][32] little-endian Lagrange coefficients at 0 of the ids, status [n]
+void launch_lagrange(const uint8_t* ids, const uint32_t* counts, uint32_t k, uint64_t n, uint8_t* coeff, int32_t* status, hipStream_t st);
 
 }  // namespace blsw
 

@@ -40,6 +40,7 @@ extern "C" {
 #define BLSW_ST_IDENTITY 4
 #define BLSW_ST_INVALID_SECRET_KEY 5
 #define BLSW_ST_BAD_INDEX 6 /* blsw_registry_verify_batch: offsets that describe no list, or an index at or beyond the registry's size */
+#define BLSW_ST_BAD_ID 7    /* blsw_lagrange_batch / blsw_recover_points_batch: a used id that is zero or equal to another used id of its list */
 
 /* Segment table of one instance's witness vector for the circuit of src/constraints.rs:335-366
  * (msg witness bytes, params Constant, pk Witness, sig Witness, then verify). Offsets are in field elements.
@@ -644,7 +645,54 @@ int blsw_aggregate_points_workspace_bytes(uint32_t group, uint64_t n, uint32_t k
 int blsw_aggregate_points_batch(uint32_t group, const uint8_t* d_in, uint32_t k, uint64_t n, uint8_t* d_out, int32_t* d_status, void* d_workspace,
                                 uint64_t workspace_bytes, void* stream);
 
-/* hash_to_g2 only (src/hasher.rs:727-740 / src/bls.rs:477-493): d_out_affine [n][24] u64 (x.c0, x.c1, y.c0, y.c1) Montgomery */
+/* Weighted point sums and threshold recovery: d_out[i] = compressed sum_{j < count_i} s_ij * P_ij for n lists of k (point, scalar) terms with
+ * caller-chosen full-size scalars, group 1 = public keys (G1, 48 bytes), group 2 = signatures (G2, 96 bytes) as in blsw_aggregate_points_batch.
+ * This is the recombination of partial signatures or share keys with Lagrange coefficients, and the check of a share key against Feldman
+ * commitments (pk_j == sum_i id_j^i C_i).
+ *   blsw_combine_points_batch  d_in [n][k][48 | 96] compressed points, d_scalars32_le [n][k][32] little-endian scalars below r (zero is legal),
+ *                              d_counts [n] (nullable: every list uses all k terms): list i uses its FIRST d_counts[i] terms; the terms behind
+ *                              have no influence, whatever their bytes. d_term_status [n][k][2] int32 (nullable): the decode status of every
+ *                              term's point and of its scalar, used or not.
+ *   blsw_lagrange_batch        d_ids32_le [n][k][32] little-endian elements of Fr -> d_coeff32_le [n][k][32]:
+ *                              lambda_j = prod_{m != j} id_m / prod_{m != j} (id_m - id_j) over the used ids — interpolation at 0; one id gives 1.
+ *                              Rows j >= count_i are zeros, and every row of a failing list is zeros.
+ *   blsw_recover_points_batch  the same sum with s_ij = lambda_ij(ids): the coefficients go into the workspace, then the combine stages run.
+ * d_status [n] int32, in the order blsw_verify_pairs_batch uses for counts, then the terms:
+ *     1. BLSW_ST_BAD_INDEX if count_i > k;
+ *     2. else BLSW_ST_IDENTITY if count_i == 0;
+ *     3. (recover and lagrange) else BLSW_ST_BAD_ENCODING for a used id >= r;
+ *     4. (recover and lagrange) else BLSW_ST_BAD_ID for a used id that is zero or equal to another used id;
+ *     5. (combine and recover) else the status of the lowest-indexed used term that is bad, the point's decode status before the scalar's
+ *        (a scalar >= r is BLSW_ST_BAD_ENCODING). A well-formed identity point is a VALID term, as it is a valid summand of
+ *        blsw_aggregate_points_batch, and so is a zero scalar;
+ *     6. else BLSW_ST_OK.
+ *   A failing list writes zeros to d_out[i]; a sum that is the identity writes the infinity encoding with BLSW_ST_OK — blsw_aggregate_points_batch's rule.
+ * BLSW_ERR_ARG before any HIP call, nothing written: a group other than 1 or 2, n == 0, k == 0 or > 65535, n * k > 0x3fffffff, a NULL among the
+ *   pointers not marked nullable. BLSW_ERR_WORKSPACE for a workspace below blsw_combine_points_workspace_bytes(group, n, k), which is
+ *   non-decreasing in n and in k and serves blsw_recover_points_batch as well (the coefficients are part of it).
+ * Workspace per term: G1 276 bytes (the decoded point 96, its status 4, the scaled Jacobian point 144, a coefficient 32); G2 4 836 bytes
+ *   (192, 4, 4 608 = the scaled point and the 15 parked Jacobian points of the ladder's table, as the signer parks them, 32); 4 bytes per list.
+ * Stages: blsw_aggregate_points_batch's decode lanes unchanged; one lane per list for the status; one lane per term for s * P — G2 by the
+ *   signer's four-digit ladder, G1 by a two-digit ladder over (x, y) -> (beta x, y) with 128 doublings in place of 255; one lane per list for the
+ *   sum, one inversion and the encoding. blsw_lagrange_batch: one lane per (list, j) with one inversion mod r, then one lane per list.
+ * Measured (tools/combine_rate.py, profiles/combine_rate.txt; 65 536 terms in lists of 4 / 16 / 128, medians of five): G2 15.5 / 16.5 / 24.7 ms
+ *   against blsw_sign_batch on 65 536 messages 16.7 / 17.2 / 18.2 ms; G1 7.0 / 7.3 / 10.0 ms against 10.4 / 10.6 / 14.0 ms with the plain 255-step
+ *   ladder. The G1 table {P, Q, P + Q} is affine (one inversion per term): with P + Q Jacobian the lanes of a wavefront walked two addition
+ *   bodies per step and the ladder was 1.05 x the plain one. The scale kernels run two waves per SIMD like the signer's; one wave, unspilled,
+ *   measured the same (6.9 / 7.1 / 10.1 ms in G1). Recovery is 1.01 - 1.04 x the combine call up to 16 terms, 1.14 x at 128 in G1. Lists of 128
+ *   terms pay a serial sum on one lane per list, as blsw_aggregate_points_batch does.
+ * All four entries are fully asynchronous on `stream`: no synchronising copy, no allocation, no event wait — they need no hash stage and hence
+ *   no step descriptor, so their arguments travel as kernel arguments, like blsw_aggregate_points_batch's.
+ * PUBLIC SCALARS ONLY: the ladders branch on the scalar's bits and on the ids, as the signer's do on the key. Shares of a secret and the secret's
+ *   recovery do not belong here. */
+int blsw_combine_points_workspace_bytes(uint32_t group, uint64_t n, uint32_t k, uint64_t* bytes);
+int blsw_combine_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_scalars32_le, const uint32_t* d_counts, uint32_t k, uint64_t n,
+                              uint8_t* d_out, int32_t* d_status, int32_t* d_term_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int blsw_lagrange_batch(const uint8_t* d_ids32_le, const uint32_t* d_counts, uint32_t k, uint64_t n, uint8_t* d_coeff32_le, int32_t* d_status, void* stream);
+int blsw_recover_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_ids32_le, const uint32_t* d_counts, uint32_t k, uint64_t n,
+                              uint8_t* d_out, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* hash_to_g2 only(src/hasher.rs:727-740 / src/bls.rs:477-493): d_out_affine [n][24] u64 (x.c0, x.c1, y.c0, y.c1) Montgomery */
 int blsw_hash_to_g2_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes);
 int blsw_hash_to_g2_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
                           void* stream);

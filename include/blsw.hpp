@@ -1446,6 +1446,103 @@ struct BLS {
         for (size_t i = 0; i < n; i++) out[i] = r[i] == 1;
         return out;
     }
+    // Weighted point sums and threshold recovery (blsw_combine_points_batch, blsw_lagrange_batch, blsw_recover_points_batch): one list per entry of
+    // the outer vector, lists of different lengths travel padded to the longest with their counts. A Scalar is 32 little-endian bytes of an element
+    // of Fr, and PUBLIC: the ladders are not constant-time. status (optional) [n] as the header states it; a failing list gives an all-zero point.
+    using Scalar = std::array<uint8_t, 32>;
+    static std::vector<Signature> combine(const std::vector<std::vector<Signature>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr) {
+        return combine_lists<Signature>(2, points, scalars, false, status);
+    }
+    static std::vector<PublicKey> combine(const std::vector<std::vector<PublicKey>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr) {
+        return combine_lists<PublicKey>(1, points, scalars, false, status);
+    }
+    // the group signature / group key from the shares' partial signatures / keys at the shares' ids (Lagrange interpolation at 0 in the exponent)
+    static std::vector<Signature> recover_signature(const std::vector<std::vector<Scalar>>& ids, const std::vector<std::vector<Signature>>& sigs, std::vector<int32_t>* status = nullptr) {
+        return combine_lists<Signature>(2, sigs, ids, true, status);
+    }
+    static std::vector<PublicKey> recover_public_key(const std::vector<std::vector<Scalar>>& ids, const std::vector<std::vector<PublicKey>>& pks, std::vector<int32_t>* status = nullptr) {
+        return combine_lists<PublicKey>(1, pks, ids, true, status);
+    }
+    // lambda_j = prod_{m != j} id_m / prod_{m != j} (id_m - id_j) per list; an empty inner vector where the list fails (status says why)
+    static std::vector<std::vector<Scalar>> lagrange_coefficients(const std::vector<std::vector<Scalar>>& ids, std::vector<int32_t>* status = nullptr) {
+        const size_t n = ids.size();
+        std::vector<uint32_t> counts;
+        const uint32_t k = pad_counts(ids, counts, "BLS::lagrange_coefficients");
+        std::vector<uint8_t> rows = pad_rows(ids, k);
+        detail::DeviceBytes d_ids(rows.size()), d_cnt(n * 4), d_coeff(rows.size()), d_st(n * 4);
+        d_ids.upload(rows.data(), rows.size());
+        d_cnt.upload(counts.data(), n * 4);
+        check(blsw_lagrange_batch(static_cast<const uint8_t*>(d_ids.get()), static_cast<const uint32_t*>(d_cnt.get()), k, n, static_cast<uint8_t*>(d_coeff.get()),
+                                  static_cast<int32_t*>(d_st.get()), nullptr),
+              "blsw_lagrange_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> st(n);
+        d_coeff.download(rows.data(), rows.size());
+        d_st.download(st.data(), n * 4);
+        std::vector<std::vector<Scalar>> out(n);
+        for (size_t i = 0; i < n; i++) {
+            if (st[i] != BLSW_ST_OK) continue;
+            out[i].resize(counts[i]);
+            for (size_t j = 0; j < counts[i]; j++) std::memcpy(out[i][j].data(), &rows[(i * k + j) * 32], 32);
+        }
+        if (status) *status = st;
+        return out;
+    }
+
+   private:
+    template <class LISTS>
+    static uint32_t pad_counts(const LISTS& lists, std::vector<uint32_t>& counts, const char* who) {
+        size_t k = 0;
+        for (const auto& l : lists) k = std::max(k, l.size());
+        if (lists.empty() || k == 0 || k > 65535) throw Error(std::string(who) + ": at least one list, 1 .. 65535 terms in the longest", BLSW_ERR_ARG);
+        counts.resize(lists.size());
+        for (size_t i = 0; i < lists.size(); i++) counts[i] = static_cast<uint32_t>(lists[i].size());
+        return static_cast<uint32_t>(k);
+    }
+    static std::vector<uint8_t> pad_rows(const std::vector<std::vector<Scalar>>& lists, uint32_t k) {
+        std::vector<uint8_t> rows(lists.size() * k * 32, 0);
+        for (size_t i = 0; i < lists.size(); i++)
+            for (size_t j = 0; j < lists[i].size(); j++) std::memcpy(&rows[(i * k + j) * 32], lists[i][j].data(), 32);
+        return rows;
+    }
+    template <class POINT>
+    static std::vector<POINT> combine_lists(uint32_t group, const std::vector<std::vector<POINT>>& points, const std::vector<std::vector<Scalar>>& rows32, bool recover,
+                                            std::vector<int32_t>* status) {
+        const size_t n = points.size(), W = sizeof(POINT::bytes);
+        const char* who = recover ? "BLS::recover" : "BLS::combine";
+        if (rows32.size() != n) throw Error(std::string(who) + ": one list of scalars or ids per list of points", BLSW_ERR_ARG);
+        for (size_t i = 0; i < n; i++)
+            if (rows32[i].size() != points[i].size()) throw Error(std::string(who) + ": one scalar or id per point", BLSW_ERR_ARG);
+        std::vector<uint32_t> counts;
+        const uint32_t k = pad_counts(points, counts, who);
+        std::vector<uint8_t> in(n * k * W, 0), rows = pad_rows(rows32, k);
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j < points[i].size(); j++) std::memcpy(&in[(i * k + j) * W], points[i][j].bytes.data(), W);
+        uint64_t bytes = 0;
+        check(blsw_combine_points_workspace_bytes(group, n, k, &bytes), "blsw_combine_points_workspace_bytes");
+        detail::DeviceBytes d_in(in.size()), d_rows(rows.size()), d_cnt(n * 4), d_out(n * W), d_st(n * 4), ws(bytes);
+        d_in.upload(in.data(), in.size());
+        d_rows.upload(rows.data(), rows.size());
+        d_cnt.upload(counts.data(), n * 4);
+        const uint8_t *p_in = static_cast<const uint8_t*>(d_in.get()), *p_rows = static_cast<const uint8_t*>(d_rows.get());
+        const uint32_t* p_cnt = static_cast<const uint32_t*>(d_cnt.get());
+        if (recover)
+            check(blsw_recover_points_batch(group, p_in, p_rows, p_cnt, k, n, static_cast<uint8_t*>(d_out.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
+                  "blsw_recover_points_batch");
+        else
+            check(blsw_combine_points_batch(group, p_in, p_rows, p_cnt, k, n, static_cast<uint8_t*>(d_out.get()), static_cast<int32_t*>(d_st.get()), nullptr, ws.get(), bytes, nullptr),
+                  "blsw_combine_points_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<uint8_t> o(n * W);
+        d_out.download(o.data(), o.size());
+        if (status) {
+            status->resize(n);
+            d_st.download(status->data(), n * 4);
+        }
+        std::vector<POINT> out(n);
+        for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[W * i], W);
+        return out;
+    }
 };
 
 }  // namespace blsw
