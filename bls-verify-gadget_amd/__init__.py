@@ -154,6 +154,10 @@ def lib():
         L.blsw_combine_points_batch.argtypes = [u32, vp, vp, vp, u32, u64, vp, vp, vp, vp, u64, vp]
         L.blsw_lagrange_batch.argtypes = [vp, vp, u32, u64, vp, vp, vp]
         L.blsw_recover_points_batch.argtypes = [u32, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
+        L.blsw_msm_workspace_bytes.argtypes = [u32, u64, u32, u32, ctypes.POINTER(u64)]
+        L.blsw_msm_points_batch.argtypes = [u32, vp, vp, vp, u32, u64, u32, vp, vp, vp, u64, vp]
+        L.blsw_registry_msm_workspace_bytes.argtypes = [u64, u64, u32, ctypes.POINTER(u64)]
+        L.blsw_registry_msm_batch.argtypes = [vp, vp, u64, vp, vp, u64, u32, vp, vp, vp, u64, vp]
         L.blsw_sign_batch.argtypes = [vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, u64, vp]
         L.blsw_verify_workspace_bytes.argtypes = [u64, u32, ctypes.POINTER(u64)]
         L.blsw_verify_batch.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp]
@@ -250,7 +254,8 @@ EXPORTED_SYMBOLS = ["blsw_version", "blsw_layout", "blsw_engine_options_default"
                     "blsw_dst_set", "blsw_dst_default", "blsw_dst_pop", "blsw_hash_to_field_batch", "blsw_pop_prove_batch", "blsw_pop_verify_batch",
                     "blsw_verify_groups_shared_workspace_bytes", "blsw_verify_groups_shared_batch", "blsw_registry_verify_shared_workspace_bytes",
                     "blsw_registry_verify_shared_batch", "blsw_combine_points_workspace_bytes", "blsw_combine_points_batch", "blsw_lagrange_batch",
-                    "blsw_recover_points_batch"] + [e + "_dst" for e in _DST_ENTRIES]
+                    "blsw_recover_points_batch", "blsw_msm_workspace_bytes", "blsw_msm_points_batch",
+                    "blsw_registry_msm_workspace_bytes", "blsw_registry_msm_batch"] + [e + "_dst" for e in _DST_ENTRIES]
 
 DST_DEFAULT = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # the library's tag: what every value entry hashes under with dst=None
 DST_POP = b"BLS_POP_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # PopProve / PopVerify of the signature draft
@@ -1090,6 +1095,31 @@ def combine_points(group, points, scalars, counts=None, want_term_status=False):
     return (out, status, term_status) if want_term_status else (out, status)
 
 
+def msm_points(group, points, scalars, counts=None, window_bits=0):
+    """combine_points for LONG lists, by the bucket method (blsw_msm_points_batch, include/blsw.h): the same arguments, and for every input both
+    accept the same (sum, status) byte for byte; k up to 2^24 terms per list; no term statuses. window_bits 0 is the library's choice from k, 1 .. 16
+    are taken as given. combine_points pays a ladder per term and sums a list on one lane; this pays about ceil(255 / window_bits) mixed additions
+    per term and a fixed tail per list: measured on ONE list the ladder wins up to 64 terms and the buckets from 256 on (65 536 terms: 48 ms in G1, 92 ms
+    in G2 against 1.7 s and 4.9 s); many short lists belong there, one or a few long lists here (tools/msm_rate.py, profiles/msm_rate.txt).
+    PUBLIC scalars only. -> (sum [n, 48 | 96] uint8, status [n] int32)."""
+    torch = _require_cuda()
+    n, k, nbytes, dev = _combine_shapes(torch, group, points, scalars, counts)
+    wb = ctypes.c_uint64(0)
+    rc = lib().blsw_msm_workspace_bytes(group, n, k, window_bits, ctypes.byref(wb))
+    if rc:
+        raise BlswError("blsw_msm_workspace_bytes failed: %d" % rc)
+    check_capacity(dev, "msm_points (n = %d, %d terms each, window_bits %d)" % (n, k, window_bits), wb.value)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((n, nbytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib().blsw_msm_points_batch(group, points.data_ptr(), scalars.data_ptr(), counts.data_ptr() if counts is not None else None, k, n, window_bits, out.data_ptr(),
+                                     status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise BlswError("blsw_msm_points_batch failed: %d" % rc)
+    torch.cuda.synchronize(dev)
+    return out, status
+
+
 def lagrange_coefficients(ids, counts=None):
     """Lagrange coefficients at 0 (blsw_lagrange_batch): ids [n, k, 32] uint8 cuda, little-endian elements of Fr, non-zero and distinct within a list's
     used ids -> (coeff [n, k, 32] uint8, status [n] int32: ST_OK, ST_BAD_INDEX, ST_IDENTITY (no id), ST_BAD_ENCODING (an id >= r) or ST_BAD_ID). Rows
@@ -1421,6 +1451,33 @@ class KeyRegistry:
     def key_status(self):
         """int32 [size] view of the keys' statuses, defined once the appends have run on their stream"""
         return self._status[:self.size]
+
+    def msm(self, indices, offsets, scalars, window_bits=0):
+        """sum_p s_p * key[index_p] per index list, by the bucket method (blsw_registry_msm_batch, include/blsw.h): list i is
+        indices[offsets[i]:offsets[i + 1]] as in registry_verify, scalars [n_indices, 32] uint8 little-endian below r, PUBLIC, one per position.
+        -> (sum48 [n, 48] uint8 — zeros for a failing list, the infinity encoding for an identity sum —, status [n] int32: ST_BAD_INDEX for bad
+        offsets or an index >= size, ST_IDENTITY for an empty list, a bad key's status, ST_BAD_ENCODING for a scalar >= r, each at the earliest bad
+        position). For an OK list the bytes are combine_points' on the gathered keys; measured on one list it is below combine_points at every
+        length from 16 terms on (it decodes nothing), 66 ms against 1.7 s at 65 536. Must be ordered behind the appends it relies on (the same stream does that)."""
+        torch = _require_cuda()
+        n, n_indices, dev = offsets.shape[0] - 1, indices.shape[0], self.device
+        assert indices.dim() == 1 and offsets.dim() == 1 and n >= 1 and scalars.shape == (n_indices, 32) and scalars.dtype == torch.uint8
+        assert indices.element_size() == 4 and offsets.element_size() == 8 and not indices.is_floating_point() and not offsets.is_floating_point()
+        assert all(t.is_contiguous() and t.device == dev for t in (indices, offsets, scalars))
+        wb = ctypes.c_uint64(0)
+        rc = lib().blsw_registry_msm_workspace_bytes(n, n_indices, window_bits, ctypes.byref(wb))
+        if rc:
+            raise BlswError("blsw_registry_msm_workspace_bytes failed: %d" % rc)
+        check_capacity(dev, "KeyRegistry.msm (n = %d, %d indices, window_bits %d)" % (n, n_indices, window_bits), wb.value)
+        ws = torch.empty(max(wb.value, 256), dtype=torch.uint8, device=dev)
+        out = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        rc = lib().blsw_registry_msm_batch(self._r, indices.data_ptr() if n_indices else None, n_indices, offsets.data_ptr(), scalars.data_ptr() if n_indices else None, n,
+                                           window_bits, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            raise BlswError("blsw_registry_msm_batch failed: %d" % rc)
+        torch.cuda.synchronize(dev)
+        return out, status
 
     def close(self):
         if getattr(self, "_r", None):

@@ -6,6 +6,7 @@
 #include <vector>
 #include "kcommon.hpp"
 #include "agg_input.hpp"
+#include "vmsm.hpp"  // the bucket method's shape functions (windows, buckets, segments, the default window)
 
 using namespace blsw;
 
@@ -2007,6 +2008,108 @@ int blsw_recover_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t
     const CombineCarve c = carve_combine(group, n, k, reinterpret_cast<char*>(d_workspace));
     launch_lagrange(d_ids32_le, d_counts, k, n, c.coeff, c.lag, st);
     launch_combine({group, k, n, d_counts, c.xy, c.pst, c.coeff, c.lag, c.scaled, nullptr, d_out, d_status}, d_in, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+// The same sum by the bucket method (k_msm.hip, vmsm.hpp). The workspace, each part 256-byte aligned: the decoded points, their statuses, the
+// histogram and the cursor [n][W][B], the sorted term indices [W][m], the bucket, segment and window sums as Jacobian rows.
+struct MsmCarve {
+    char* part[9];
+    uint64_t bytes;
+};
+static MsmCarve carve_msm(uint32_t group, uint64_t n, uint32_t k, uint32_t c, char* base) {
+    const uint64_t m = n * k, rows = n * msm_windows(c), jac = (group == 1 ? 3 : 6) * sizeof(Fp);
+    const uint64_t size[8] = {m * (group == 1 ? 2 : 4) * sizeof(Fp), m * sizeof(int32_t), rows * msm_buckets(c) * sizeof(uint32_t), rows * msm_buckets(c) * sizeof(uint32_t),
+                              msm_windows(c) * m * sizeof(uint32_t), rows * msm_buckets(c) * jac, rows * msm_segments(c) * jac, rows * jac};
+    MsmCarve v;
+    uint64_t off = 0;
+    for (int i = 0; i < 8; i++) {
+        v.part[i] = base + off;
+        off += align_up(size[i], 256);
+    }
+    v.bytes = off;
+    return v;
+}
+static bool msm_shape_ok(uint32_t group, uint64_t n, uint32_t k, uint32_t window_bits) {
+    return (group == 1 || group == 2) && n != 0 && k != 0 && k <= BLSW_MSM_MAX_K && n <= 0x3fffffffu / k && window_bits <= BLSW_MSM_MAX_WINDOW;
+}
+int blsw_msm_workspace_bytes(uint32_t group, uint64_t n, uint32_t k, uint32_t window_bits, uint64_t* bytes) {
+    if (!bytes || !msm_shape_ok(group, n, k, window_bits)) return BLSW_ERR_ARG;
+    *bytes = carve_msm(group, n, k, window_bits ? window_bits : msm_default_window(k), nullptr).bytes;
+    return BLSW_OK;
+}
+int blsw_msm_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_scalars32_le, const uint32_t* d_counts, uint32_t k, uint64_t n, uint32_t window_bits,
+                          uint8_t* d_out, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    uint64_t need = 0;
+    if (!d_in || !d_scalars32_le || !d_out || !d_status || !d_workspace || blsw_msm_workspace_bytes(group, n, k, window_bits, &need)) return BLSW_ERR_ARG;
+    if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(stream_device(st));
+    const uint32_t c = window_bits ? window_bits : msm_default_window(k);
+    const MsmCarve v = carve_msm(group, n, k, c, reinterpret_cast<char*>(d_workspace));
+    launch_msm({group, k, c, n, d_counts, reinterpret_cast<Fp*>(v.part[0]), reinterpret_cast<int32_t*>(v.part[1]), d_scalars32_le, reinterpret_cast<uint32_t*>(v.part[2]),
+                reinterpret_cast<uint32_t*>(v.part[3]), reinterpret_cast<uint32_t*>(v.part[4]), reinterpret_cast<Fp*>(v.part[5]), reinterpret_cast<Fp*>(v.part[6]),
+                reinterpret_cast<Fp*>(v.part[7]), d_out, d_status},
+               d_in, st);
+    return hip_ok(hipGetLastError(), "launch");
+}
+// The registry form. The workspace: the histogram and the cursor [n][W][B], the sorted positions [W][n_indices], the claims and owners
+// [n_indices], the serial flags [n], the bucket, segment and window sums. The library's choice of c goes by the mean list length.
+static uint32_t registry_msm_window(uint64_t n, uint64_t n_indices, uint32_t window_bits) {
+    if (window_bits) return window_bits;
+    const uint64_t mean = (n_indices + n - 1) / n;
+    return msm_default_window(mean == 0 ? 1 : mean > BLSW_MSM_MAX_K ? BLSW_MSM_MAX_K : (uint32_t)mean);
+}
+static MsmCarve carve_registry_msm(uint64_t n, uint64_t n_indices, uint32_t c, char* base) {
+    const uint64_t rows = n * msm_windows(c), jac = 3 * sizeof(Fp);
+    const uint64_t size[9] = {rows * msm_buckets(c) * sizeof(uint32_t), rows * msm_buckets(c) * sizeof(uint32_t), msm_windows(c) * n_indices * sizeof(uint32_t),
+                              n_indices * sizeof(uint32_t), n_indices * sizeof(uint32_t), n * sizeof(int32_t), rows * msm_buckets(c) * jac, rows * msm_segments(c) * jac, rows * jac};
+    MsmCarve v;
+    uint64_t off = 0;
+    for (int i = 0; i < 9; i++) {
+        v.part[i] = base + off;
+        off += align_up(size[i], 256);
+    }
+    v.bytes = off;
+    return v;
+}
+int blsw_registry_msm_workspace_bytes(uint64_t n, uint64_t n_indices, uint32_t window_bits, uint64_t* bytes) {
+    if (!bytes || n == 0 || n > 0x7fffffffu || n_indices > (1ull << 40) || window_bits > BLSW_MSM_MAX_WINDOW) return BLSW_ERR_ARG;
+    *bytes = carve_registry_msm(n, n_indices, registry_msm_window(n, n_indices, window_bits), nullptr).bytes;
+    return BLSW_OK;
+}
+int blsw_registry_msm_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_scalars32_le, uint64_t n,
+                            uint32_t window_bits, uint8_t* d_out48, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream_) {
+    uint64_t need = 0;
+    if (!r || !d_offsets || !d_out48 || !d_status || !d_workspace || (!d_indices && n_indices) || (!d_scalars32_le && n_indices) || r->size == 0 ||
+        blsw_registry_msm_workspace_bytes(n, n_indices, window_bits, &need))
+        return BLSW_ERR_ARG;
+    if (workspace_bytes < need) return BLSW_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+    DeviceGuard guard(r->device);
+    const uint32_t c = registry_msm_window(n, n_indices, window_bits);
+    const MsmCarve v = carve_registry_msm(n, n_indices, c, reinterpret_cast<char*>(d_workspace));
+    MsmArgs a = {};
+    a.group = 1;
+    a.c = c;
+    a.n = n;
+    a.scalars = d_scalars32_le;
+    a.hist = reinterpret_cast<uint32_t*>(v.part[0]);
+    a.cursor = reinterpret_cast<uint32_t*>(v.part[1]);
+    a.sorted = reinterpret_cast<uint32_t*>(v.part[2]);
+    a.claims = reinterpret_cast<uint32_t*>(v.part[3]);
+    a.owner = reinterpret_cast<uint32_t*>(v.part[4]);
+    a.serial = reinterpret_cast<int32_t*>(v.part[5]);
+    a.buckets = reinterpret_cast<Fp*>(v.part[6]);
+    a.segments = reinterpret_cast<Fp*>(v.part[7]);
+    a.windows = reinterpret_cast<Fp*>(v.part[8]);
+    a.out = d_out48;
+    a.status = d_status;
+    a.offsets = d_offsets;
+    a.indices = d_indices;
+    a.n_indices = n_indices;
+    a.records = r->records;
+    a.size = r->size;
+    launch_msm_registry(a, st);
     return hip_ok(hipGetLastError(), "launch");
 }
 int blsw_hash_to_g2_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes) {

@@ -889,6 +889,38 @@ struct CombineArgs {
 void launch_combine(const CombineArgs& a, const uint8_t* in, hipStream_t st);
 // coeff [n][k][32] little-endian Lagrange coefficients at 0 of the ids, status [n]
 void launch_lagrange(const uint8_t* ids, const uint32_t* counts, uint32_t k, uint64_t n, uint8_t* coeff, int32_t* status, hipStream_t st);
+// blsw_msm_points_batch (k_msm.hip, vmsm.hpp): the same n lists of k terms by the bucket method, c = window bits, W windows, B = 2^c buckets,
+// S segments per window; point rows are element-major (row * lanes + lane)
+struct MsmArgs {
+    uint32_t group, k, c;
+    uint64_t n;
+    const uint32_t* counts;  // [n], nullable
+    const Fp* xy;            // [m][2 | 4] decoded points (k_decode_points)
+    const int32_t* pst;      // [m] their decode statuses
+    const uint8_t* scalars;  // [m][32] little-endian
+    uint32_t* hist;          // [n][W][B] counts, then their exclusive prefix per (list, window)
+    uint32_t* cursor;        // [n][W][B] the scatter's cursor: a bucket's end once the scatter has run
+    uint32_t* sorted;        // [W][m] term indices in bucket order, list i's at [w][i k ..)
+    Fp* buckets;             // [3 | 6][n W B] Jacobian bucket sums
+    Fp* segments;            // [3 | 6][n W S]
+    Fp* windows;             // [3 | 6][n W]
+    uint8_t* out;            // [n][48 | 96]
+    int32_t* status;         // [n]
+    // the registry form (blsw_registry_msm_batch; group 1, k unused): list i = indices[offsets[i] .. offsets[i + 1]), sorted is [W][n_indices] and
+    // holds positions relative to the list's first
+    const uint64_t* offsets;  // [n + 1]
+    const uint32_t* indices;  // [n_indices]
+    uint64_t n_indices;
+    const void* records;      // the registry's 128-byte records
+    uint32_t size;            // the registry's size as of the call
+    uint32_t* claims;         // [n_indices] OK lists that hold the position
+    uint32_t* owner;          // [n_indices] the list that holds it, where there is one
+    int32_t* serial;          // [n] 1: the list shares a position and is summed by its own lane
+};
+// decode of `in`, the lists' statuses, histogram, scan, scatter, bucket sums, window reduction, final sum
+void launch_msm(const MsmArgs& a, const uint8_t* in, hipStream_t st);
+// the same over registry records: the lists' statuses and claims, then the stages from the histogram on
+void launch_msm_registry(const MsmArgs& a, hipStream_t st);
 
 }  // namespace blsw
 

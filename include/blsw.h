@@ -692,6 +692,42 @@ int blsw_lagrange_batch(const uint8_t* d_ids32_le, const uint32_t* d_counts, uin
 int blsw_recover_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_ids32_le, const uint32_t* d_counts, uint32_t k, uint64_t n,
                               uint8_t* d_out, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
+/* The same sum for LONG lists, by the bucket method (csrc/vmsm.hpp). New symbols only: the ABI number stays 17.
+ *   blsw_msm_points_batch has blsw_combine_points_batch's contract word for word: d_in, d_scalars32_le, d_counts (nullable), group 1 / 2, the
+ *   six-step status order, zeros for a failing list, the infinity encoding with BLSW_ST_OK for an identity sum, a well-formed identity point and a
+ *   zero scalar as valid terms. For every input both entries accept, d_out and d_status are byte for byte what blsw_combine_points_batch writes.
+ *   There is no d_term_status. k may go up to 2^24 (16 777 216); n * k <= 0x3fffffff still holds.
+ *   window_bits: 0 = the library's choice from k (csrc/vmsm.hpp: msm_default_window); 1 .. 16 are taken as given (tuning, and tests reach every
+ *   path at small k with it).
+ * BLSW_ERR_ARG before any HIP call, nothing written: a group other than 1 or 2, n == 0, k == 0 or > 2^24, n * k > 0x3fffffff, window_bits > 16, a
+ *   NULL among the pointers not marked nullable. BLSW_ERR_WORKSPACE for a workspace below blsw_msm_workspace_bytes(group, n, k, window_bits),
+ *   which is non-decreasing in n and in k for a fixed window_bits (0 included).
+ * Workspace with c = window bits, W = ceil(255 / c), B = 2^c: per term the decoded point and its status (G1 100, G2 196 bytes) and 4 W bytes of
+ *   sorted indices; per list 8 W B bytes of counts and cursors and W (B + ceil(B / 32) + 1) Jacobian points of 144 (G1) or 288 (G2) bytes.
+ * Stages: blsw_aggregate_points_batch's decode lanes and the combine entry's status rule unchanged; one lane per term counts its non-zero c-bit
+ *   digits into a histogram per (list, window); a prefix scan; one lane per term scatters its index into bucket order through an atomic cursor;
+ *   one lane per (list, window, bucket) adds its bucket's points; one lane per 32 buckets and then one per (list, window) form sum_b b B_b; one lane
+ *   per list combines the windows, inverts once and encodes. The order inside a bucket is not fixed; every addition is the complete four-branch
+ *   form, so the sum — a group element — and its bytes are.
+ * Measured (tools/msm_rate.py, profiles/msm_rate.txt; MI355X, ONE list, medians of five, the existing path in the same run): 65 536 terms G1
+ *   48 ms, G2 92 ms, blsw_registry_msm_batch 66 ms, against blsw_combine_points_batch on 65 535 + 1 terms and blsw_aggregate_points_batch
+ *   1 725 ms and 4 914 ms (spreads 436 and 1 351 ms); 2^20 terms 0.50 s, 0.64 s and 0.96 s against 2.0 s and 5.4 s. Half of the call at 65 536
+ *   terms and four fifths at 2^20 is the status rule, which walks the list on one lane (profiles/msm_stages.txt).
+ * One long bucket: when all scalars are equal, one bucket per window takes every term and one lane adds them one after the other. The result is
+ *   right; the time is that of k serial mixed additions and is not hidden — measured at 65 536 equal scalars: G1 1.46 s, G2 4.48 s, about what
+ *   the combine entry's one-lane sum takes. Long buckets are not split. A window of 2 or 3 bits is the same effect (4 .. 8 buckets share all
+ *   terms): with c = 7, 9, 11, 12 or 14 the top window is that narrow (65 536 terms, G1: 219 .. 360 ms instead of 48), so the library's choice is
+ *   among 5, 8, 13 and 15.
+ * Which entry: blsw_combine_points_batch pays a ladder per term and sums a list on one lane, this entry pays about W mixed additions per term and
+ *   a fixed tail of a few hundred additions per list. Measured on one list, the per-term ladder wins up to 64 terms (G1 8.0 against 8.4 ms, G2
+ *   17.6 against 21.8 ms) and the buckets from 256 terms on (9.8 against 12.7 ms, 22.0 against 32.6 ms; 3.6 x at 1 024, 10 x at 4 096): the
+ *   crossover lies between 64 and 256 terms of ONE list. Many short lists fill the device with ladders and belong there.
+ * Fully asynchronous on `stream`: no synchronising copy, no allocation, no event wait. PUBLIC SCALARS ONLY: the digits and the bucket indices
+ *   depend on the scalars. */
+int blsw_msm_workspace_bytes(uint32_t group, uint64_t n, uint32_t k, uint32_t window_bits, uint64_t* bytes);
+int blsw_msm_points_batch(uint32_t group, const uint8_t* d_in, const uint8_t* d_scalars32_le, const uint32_t* d_counts, uint32_t k, uint64_t n,
+                          uint32_t window_bits, uint8_t* d_out, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
 /* hash_to_g2 only(src/hasher.rs:727-740 / src/bls.rs:477-493): d_out_affine [n][24] u64 (x.c0, x.c1, y.c0, y.c1) Montgomery */
 int blsw_hash_to_g2_workspace_bytes(uint64_t n, uint32_t msg_len, uint64_t* bytes);
 int blsw_hash_to_g2_batch(const uint8_t* d_msg, uint32_t msg_len, uint64_t n, uint64_t* d_out_affine, void* d_workspace, uint64_t workspace_bytes,
@@ -868,6 +904,27 @@ int blsw_registry_verify_workspace_bytes(uint64_t n, uint32_t msg_len, uint32_t 
 int blsw_registry_verify_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_sig96,
                                const uint8_t* d_msg, uint32_t msg_len, uint64_t n, const uint64_t* d_scalars, uint32_t group, int32_t* d_result, int32_t* d_status,
                                uint8_t* d_agg48, void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* sum_p s_p * key[index_p] over index lists of a registry, by the bucket method of blsw_msm_points_batch (G1 only; new symbols, ABI 17): list i is
+ * d_indices[d_offsets[i] .. d_offsets[i + 1]) in CSR form as above, position p of d_indices carries the scalar d_scalars32_le[p] (32 little-endian
+ * bytes below r, PUBLIC). No key is decoded: the records are read as they stand. d_status [n] int32, in this order:
+ *     1. BLSW_ST_BAD_INDEX for bad offsets, by rule 1 above: no entry of the list is read;
+ *     2. else BLSW_ST_IDENTITY for an empty list (the combine rule);
+ *     3. else the status of the EARLIEST LIST POSITION that is bad; within a position: an index >= size as of the call is BLSW_ST_BAD_INDEX and its
+ *        record is never read; a key whose status is neither OK nor IDENTITY gives that status; a scalar >= r is BLSW_ST_BAD_ENCODING;
+ *     4. else BLSW_ST_OK.
+ *   A repeated index counts as often as it occurs; an identity key and a zero scalar are valid terms. d_out48 [n][48]: zeros for a failing list,
+ *   the infinity encoding for an identity sum; for an OK list the bytes blsw_combine_points_batch gives on the gathered keys.
+ *   window_bits as in blsw_msm_points_batch; 0 chooses by the MEAN list length n_indices / n.
+ * BLSW_ERR_ARG before any HIP call, nothing written: n == 0 or > 0x7fffffff, a NULL among r, d_offsets, d_out48, d_status, d_workspace,
+ *   d_indices or d_scalars32_le NULL with n_indices != 0, n_indices > 2^40, a registry of size 0, window_bits > 16. BLSW_ERR_WORKSPACE below
+ *   blsw_registry_msm_workspace_bytes(n, n_indices, window_bits): non-decreasing in n and in n_indices for window_bits 1 .. 16, and in n_indices
+ *   for window_bits 0 (there more lists over the same indices are shorter lists and may get narrower windows).
+ * Lists that are valid one by one can share positions when a bad list lies between them (offsets 0, 5, 3, 8); such lists are summed by one lane
+ *   each with the per-term ladder — the same bytes, the combine entry's speed. The status lane walks its list once, one lane per list.
+ * Must be ordered behind the appends it relies on, like the verify call. Fully asynchronous on `stream`. */
+int blsw_registry_msm_workspace_bytes(uint64_t n, uint64_t n_indices, uint32_t window_bits, uint64_t* bytes);
+int blsw_registry_msm_batch(const blsw_registry_t* r, const uint32_t* d_indices, uint64_t n_indices, const uint64_t* d_offsets, const uint8_t* d_scalars32_le,
+                            uint64_t n, uint32_t window_bits, uint8_t* d_out48, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes, void* stream);
 
 /* A CALLER-CHOSEN DOMAIN SEPARATION TAG for the value entries, and PopProve / PopVerify. New symbols only: the ABI number stays 17 and
  * blsw_engine_options_t is untouched. Every entry above hashes under the library's tag, BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_; the *_dst

@@ -217,6 +217,44 @@ class KeyRegistry {
         return st;
     }
 
+    // sum_p s_p * key[index_p] per list, by the bucket method (blsw_registry_msm_batch): one list of indices and one of scalars (32 little-endian
+    // bytes below r, PUBLIC) per entry of the outer vectors. status (optional) [n] as the header states it; a failing list gives an all-zero key.
+    std::vector<PublicKey> msm(const std::vector<std::vector<uint32_t>>& indices, const std::vector<std::vector<std::array<uint8_t, 32>>>& scalars,
+                               std::vector<int32_t>* status = nullptr, uint32_t window_bits = 0) const {
+        const size_t n = indices.size();
+        if (n == 0 || scalars.size() != n) throw Error("KeyRegistry::msm: one list of scalars per list of indices, at least one list", BLSW_ERR_ARG);
+        std::vector<uint64_t> offsets(n + 1, 0);
+        std::vector<uint32_t> flat;
+        std::vector<uint8_t> rows;
+        for (size_t i = 0; i < n; i++) {
+            if (scalars[i].size() != indices[i].size()) throw Error("KeyRegistry::msm: one scalar per index", BLSW_ERR_ARG);
+            flat.insert(flat.end(), indices[i].begin(), indices[i].end());
+            for (const auto& sc : scalars[i]) rows.insert(rows.end(), sc.begin(), sc.end());
+            offsets[i + 1] = flat.size();
+        }
+        uint64_t bytes = 0;
+        check(blsw_registry_msm_workspace_bytes(n, flat.size(), window_bits, &bytes), "blsw_registry_msm_workspace_bytes");
+        const OnDevice on(device_);
+        detail::DeviceBytes d_idx(flat.size() * 4 + 4), d_off(offsets.size() * 8), d_sc(rows.size() + 32), d_out(n * 48), d_st(n * 4), ws(bytes + 256);
+        if (!flat.empty()) d_idx.upload(flat.data(), flat.size() * 4);
+        if (!rows.empty()) d_sc.upload(rows.data(), rows.size());
+        d_off.upload(offsets.data(), offsets.size() * 8);
+        check(blsw_registry_msm_batch(r_, flat.empty() ? nullptr : static_cast<const uint32_t*>(d_idx.get()), flat.size(), static_cast<const uint64_t*>(d_off.get()),
+                                      flat.empty() ? nullptr : static_cast<const uint8_t*>(d_sc.get()), n, window_bits, static_cast<uint8_t*>(d_out.get()),
+                                      static_cast<int32_t*>(d_st.get()), ws.get(), bytes + 256, nullptr),
+              "blsw_registry_msm_batch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<uint8_t> o(n * 48);
+        d_out.download(o.data(), o.size());
+        if (status) {
+            status->resize(n);
+            d_st.download(status->data(), n * 4);
+        }
+        std::vector<PublicKey> out(n);
+        for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &o[48 * i], 48);
+        return out;
+    }
+
     int device() const { return device_; }
 
    private:
@@ -1451,17 +1489,27 @@ struct BLS {
     // of Fr, and PUBLIC: the ladders are not constant-time. status (optional) [n] as the header states it; a failing list gives an all-zero point.
     using Scalar = std::array<uint8_t, 32>;
     static std::vector<Signature> combine(const std::vector<std::vector<Signature>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr) {
-        return combine_lists<Signature>(2, points, scalars, false, status);
+        return combine_lists<Signature>(2, points, scalars, Sum::Ladders, status);
     }
     static std::vector<PublicKey> combine(const std::vector<std::vector<PublicKey>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr) {
-        return combine_lists<PublicKey>(1, points, scalars, false, status);
+        return combine_lists<PublicKey>(1, points, scalars, Sum::Ladders, status);
+    }
+    // The same sums by the bucket method (blsw_msm_points_batch): lists of up to 2^24 terms; window_bits 0 is the library's choice. For every input
+    // combine accepts the points and statuses are the same bytes; the header says which of the two suits which shape.
+    static std::vector<Signature> msm(const std::vector<std::vector<Signature>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr,
+                                      uint32_t window_bits = 0) {
+        return combine_lists<Signature>(2, points, scalars, Sum::Buckets, status, window_bits);
+    }
+    static std::vector<PublicKey> msm(const std::vector<std::vector<PublicKey>>& points, const std::vector<std::vector<Scalar>>& scalars, std::vector<int32_t>* status = nullptr,
+                                      uint32_t window_bits = 0) {
+        return combine_lists<PublicKey>(1, points, scalars, Sum::Buckets, status, window_bits);
     }
     // the group signature / group key from the shares' partial signatures / keys at the shares' ids (Lagrange interpolation at 0 in the exponent)
     static std::vector<Signature> recover_signature(const std::vector<std::vector<Scalar>>& ids, const std::vector<std::vector<Signature>>& sigs, std::vector<int32_t>* status = nullptr) {
-        return combine_lists<Signature>(2, sigs, ids, true, status);
+        return combine_lists<Signature>(2, sigs, ids, Sum::Recover, status);
     }
     static std::vector<PublicKey> recover_public_key(const std::vector<std::vector<Scalar>>& ids, const std::vector<std::vector<PublicKey>>& pks, std::vector<int32_t>* status = nullptr) {
-        return combine_lists<PublicKey>(1, pks, ids, true, status);
+        return combine_lists<PublicKey>(1, pks, ids, Sum::Recover, status);
     }
     // lambda_j = prod_{m != j} id_m / prod_{m != j} (id_m - id_j) per list; an empty inner vector where the list fails (status says why)
     static std::vector<std::vector<Scalar>> lagrange_coefficients(const std::vector<std::vector<Scalar>>& ids, std::vector<int32_t>* status = nullptr) {
@@ -1491,10 +1539,10 @@ struct BLS {
 
    private:
     template <class LISTS>
-    static uint32_t pad_counts(const LISTS& lists, std::vector<uint32_t>& counts, const char* who) {
+    static uint32_t pad_counts(const LISTS& lists, std::vector<uint32_t>& counts, const char* who, size_t max_k = 65535) {
         size_t k = 0;
         for (const auto& l : lists) k = std::max(k, l.size());
-        if (lists.empty() || k == 0 || k > 65535) throw Error(std::string(who) + ": at least one list, 1 .. 65535 terms in the longest", BLSW_ERR_ARG);
+        if (lists.empty() || k == 0 || k > max_k) throw Error(std::string(who) + ": at least one list, 1 .. " + std::to_string(max_k) + " terms in the longest", BLSW_ERR_ARG);
         counts.resize(lists.size());
         for (size_t i = 0; i < lists.size(); i++) counts[i] = static_cast<uint32_t>(lists[i].size());
         return static_cast<uint32_t>(k);
@@ -1505,21 +1553,27 @@ struct BLS {
             for (size_t j = 0; j < lists[i].size(); j++) std::memcpy(&rows[(i * k + j) * 32], lists[i][j].data(), 32);
         return rows;
     }
+    // which C entry forms the sums: blsw_combine_points_batch, blsw_recover_points_batch, blsw_msm_points_batch (the only one that reads window_bits)
+    enum class Sum { Ladders, Recover, Buckets };
     template <class POINT>
-    static std::vector<POINT> combine_lists(uint32_t group, const std::vector<std::vector<POINT>>& points, const std::vector<std::vector<Scalar>>& rows32, bool recover,
-                                            std::vector<int32_t>* status) {
+    static std::vector<POINT> combine_lists(uint32_t group, const std::vector<std::vector<POINT>>& points, const std::vector<std::vector<Scalar>>& rows32, Sum how,
+                                            std::vector<int32_t>* status, uint32_t window_bits = 0) {
         const size_t n = points.size(), W = sizeof(POINT::bytes);
-        const char* who = recover ? "BLS::recover" : "BLS::combine";
+        const bool msm = how == Sum::Buckets, recover = how == Sum::Recover;
+        const char* who = recover ? "BLS::recover" : msm ? "BLS::msm" : "BLS::combine";
         if (rows32.size() != n) throw Error(std::string(who) + ": one list of scalars or ids per list of points", BLSW_ERR_ARG);
         for (size_t i = 0; i < n; i++)
             if (rows32[i].size() != points[i].size()) throw Error(std::string(who) + ": one scalar or id per point", BLSW_ERR_ARG);
         std::vector<uint32_t> counts;
-        const uint32_t k = pad_counts(points, counts, who);
+        const uint32_t k = pad_counts(points, counts, who, msm ? size_t(1) << 24 : 65535);
         std::vector<uint8_t> in(n * k * W, 0), rows = pad_rows(rows32, k);
         for (size_t i = 0; i < n; i++)
             for (size_t j = 0; j < points[i].size(); j++) std::memcpy(&in[(i * k + j) * W], points[i][j].bytes.data(), W);
         uint64_t bytes = 0;
-        check(blsw_combine_points_workspace_bytes(group, n, k, &bytes), "blsw_combine_points_workspace_bytes");
+        if (msm)
+            check(blsw_msm_workspace_bytes(group, n, k, window_bits, &bytes), "blsw_msm_workspace_bytes");
+        else
+            check(blsw_combine_points_workspace_bytes(group, n, k, &bytes), "blsw_combine_points_workspace_bytes");
         detail::DeviceBytes d_in(in.size()), d_rows(rows.size()), d_cnt(n * 4), d_out(n * W), d_st(n * 4), ws(bytes);
         d_in.upload(in.data(), in.size());
         d_rows.upload(rows.data(), rows.size());
@@ -1529,6 +1583,10 @@ struct BLS {
         if (recover)
             check(blsw_recover_points_batch(group, p_in, p_rows, p_cnt, k, n, static_cast<uint8_t*>(d_out.get()), static_cast<int32_t*>(d_st.get()), ws.get(), bytes, nullptr),
                   "blsw_recover_points_batch");
+        else if (msm)
+            check(blsw_msm_points_batch(group, p_in, p_rows, p_cnt, k, n, window_bits, static_cast<uint8_t*>(d_out.get()), static_cast<int32_t*>(d_st.get()), ws.get(),
+                                        bytes, nullptr),
+                  "blsw_msm_points_batch");
         else
             check(blsw_combine_points_batch(group, p_in, p_rows, p_cnt, k, n, static_cast<uint8_t*>(d_out.get()), static_cast<int32_t*>(d_st.get()), nullptr, ws.get(), bytes, nullptr),
                   "blsw_combine_points_batch");
